@@ -22,6 +22,11 @@ Rank 0 prints ONE JSON line.  Beyond the driver's contract it carries
                  warm-up steps; then untimed frames until 1 s has passed since the first one, so that a process that
                  starts on an idle GPU measures its sustained clocks whatever W and K are; all of them are reported as
                  "pre_warm_frames" / "pre_warm_seconds").
+  --dump-outputs DIR : after the timed steps, what the last timed step computed -- the forward's output tensors and
+                 the gradients of the Gaussians' parameters, as a caller of render_gaussians receives them (rank 0's
+                 under N > 1) -- is written as DIR/<name>.npy in float32 / float64, at most DUMP_BYTES in all: an array
+                 that does not fit its share is a fixed, seeded sample of its rows (pixels for per-pixel arrays), so
+                 that two builds run with the same arguments can be compared output for output.
 Defaults: K = 100, W = 20 (SURVEY 8d asks for >= 50 iterations after >= 10 warm-ups); the default run takes about 20 s,
 most of it scene generation and the CPU baseline.
 """
@@ -47,6 +52,8 @@ VALU_ISSUE_NS, NUM_SIMDS = 1.1, 1024  # tools/ubench/valu_rate.hip; 256 CUs x 4 
 STAGE_FRAMES = 20  # untimed frames of the per-stage table, run before the warm-up
 PRE_WARM_SECONDS = 1.0  # ... followed by untimed frames until this much time has passed since the first frame
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_BYTES = 60 << 20  # --dump-outputs: total size of the written arrays (under 64 MB with the .npy headers)
+DUMP_SEED = 0  # --dump-outputs: seed of the row sample of an array larger than its share
 
 
 def algorithmic_bytes(N, V, K, T, P, F, C, D):
@@ -80,6 +87,47 @@ def survey_bytes(N, V, K, T, P, F, C, D, backward, kb=8):
     return b_fwd, (b_bwd if backward else 0)
 
 
+PIXEL_OUTPUTS = ("image", "image_weight", "depth", "depth_var", "median_depth")  # (H, W[, C]) -> sampled by pixel
+POINT_OUTPUTS = ("points_in_view", "point_depth", "point_visibility", "point_heuristic", "gaussians2d")
+
+
+def step_outputs(r, grad_holder):
+    """name -> float32 / float64 numpy array: what one step handed its caller (the forward's tensors, then the
+    parameter gradients; integer tensors as float64, which holds them exactly)."""
+    out = {}
+    for name in PIXEL_OUTPUTS + POINT_OUTPUTS:
+        t = getattr(r, name, None)
+        if t is not None:
+            t = t.detach().cpu()
+            out[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    for name, t in (grad_holder.items() if grad_holder is not None else ()):
+        if t.grad is not None:
+            out[f"grad_{name}"] = t.grad.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(arrays, out_dir):
+    """Write every array as out_dir/<name>.npy within DUMP_BYTES: the smallest arrays are kept whole, the rest share
+    what is left equally, each as a sorted, seeded sample of its rows (per-pixel arrays: of their pixels), so the sample
+    depends only on the array's shape.  Returns name -> [full shape, rows written]."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left, record = DUMP_BYTES, {}
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0]))
+    for i, (name, a) in enumerate(items):
+        shape = list(a.shape)
+        rows = a.reshape(-1, *a.shape[2:]) if name in PIXEL_OUTPUTS else a
+        row_bytes = max(1, rows.itemsize * (rows.size // max(1, rows.shape[0])))
+        keep = min(rows.shape[0], left // (len(items) - i) // row_bytes)
+        if keep < rows.shape[0]:
+            pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(DUMP_SEED))[:keep]
+            a = rows[pick.sort().values.numpy()]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        record[name] = [shape, int(keep)]
+    return record
+
+
 def launch_command(args, port=None):
     """The one-node multi-rank launch of this script: one process per GPU over RCCL (torch.distributed.run)."""
     import socket
@@ -98,6 +146,8 @@ def launch_command(args, port=None):
     if args.interleave:
         cmd += ["--interleave", str(args.interleave)]
     cmd += ["--exchange", args.exchange, "--grad-mode", args.grad_mode]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return cmd
 
 
@@ -119,7 +169,11 @@ def main():
                          "optimizer; implies the sparse exchange)")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="print the multi-rank launch command for --gpus N and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; see the docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N without a launcher around us: start the N ranks ourselves, as a CHILD process (never exec: this
     # process may already hold the GPU), relay its output and exit with its code.  No GPU call happens before this.
@@ -266,11 +320,18 @@ def main():
     nv.timer.only = {dominant}
     nv.timer.enabled = not args.no_kernel_timing
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()  # kept for --dump-outputs
     sync()
     elapsed = time.perf_counter() - t0
     nv.timer.enabled = False
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dict(dir=args.dump_outputs, seed=DUMP_SEED,
+                      arrays=dump_outputs(step_outputs(last, grad_holder if wl["backward"] else None),
+                                          args.dump_outputs))
+    del last
     timed_records = nv.timer.summary() if nv.timer.records else {}
     allreduce = None
     if world > 1:
@@ -427,6 +488,8 @@ def main():
             # decomposition of ms_per_step (the bracketing itself costs host time; the sum is a few % above it)
             "stages_ms_untimed_pass": {k: round(v["ms_per_step"], 4) for k, v in sorted(stages.items())
                                        if "ms_per_step" in v},
+            # --dump-outputs: name -> [full shape, rows written]
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out), flush=True)
     if world > 1:

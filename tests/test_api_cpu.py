@@ -259,3 +259,33 @@ def test_row_shard_matches_the_c_side_numbering():
     assert (c.row_begin, c.row_end, c.band, c.period, c.phase) == (0, 16, 2, 3, 1)
     s = parallel.shard_for(2, 3, 250, 16)
     assert s.period == 1 and s.rows() == list(range(s.row_begin, s.row_end)) and s.bands[-1][1] == 250
+
+
+def test_bench_dump_outputs_fits_and_repeats(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays only, at most 64 MB in all however large the frame, and the
+    same seeded sample of an oversized array every time"""
+    import os
+    import sys
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    n, v = 600_000, 500_000
+    r = types.SimpleNamespace(image=torch.rand(1024, 2048, 3), image_weight=torch.rand(1024, 2048),
+                              points_in_view=torch.arange(v), point_depth=torch.rand(v, 1), gaussians2d=torch.rand(v, 7))
+    holder = {k: torch.zeros(s) for k, s in dict(position=(n, 3), rotation=(n, 4), feature=(n, 3, 16)).items()}
+    for t in holder.values():
+        t.grad = torch.rand(t.shape)
+    arrays = bench.step_outputs(r, holder)
+    assert sum(a.nbytes for a in arrays.values()) > (64 << 20)
+    rec = [bench.dump_outputs(arrays, str(tmp_path / d)) for d in ("a", "b")]
+    assert rec[0] == rec[1] and rec[0]["image"][0] == [1024, 2048, 3] and rec[0]["point_depth"][1] == v
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"{k}.npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "points_in_view.npy"), np.arange(v, dtype=np.float64))
