@@ -117,7 +117,8 @@ def _run_modes(rank, world, port, size, n, depth_mode, interleave, grad_mode, fr
 @pytest.mark.parametrize("depth_mode,interleave,world,size,grad_mode", [
     (False, 0, 2, (320, 256), "replicated"), (True, 2, 3, (320, 250), "replicated"),
     (True, 0, 3, (320, 30), "replicated"),            # rank 2 owns no tile row: an empty list
-    (False, 0, 2, (320, 256), "sharded"), (True, 3, 3, (320, 250), "sharded")])
+    (False, 0, 2, (320, 256), "sharded"), (True, 3, 3, (320, 250), "sharded"),
+    (True, 0, 3, (320, 30), "sharded")])              # the rowless rank through the stages, then gs_frame_fwd
 def test_fused_sharded_frame_sparse_exchange(tmp_path, depth_mode, interleave, world, size, grad_mode):
     """the fused frame's sparse exchange under a real process group (gloo ranks sharing the GPU): lists of the touched
     splats instead of dense rows; "replicated": every rank ends with the single-process gradients and all ranks with the
