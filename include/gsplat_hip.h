@@ -409,20 +409,10 @@ typedef struct GsFrameLayout {
   int32_t num_features, grad_row_floats, tiles_x, tiles_y, local_height;
 } GsFrameLayout;
 
-/* Optional fork of gs_frame_fwd (host struct of caller-owned handles, NULL = everything on `stream`): the colour stage
- * (SH evaluation / feature gather) is enqueued on side_stream (a hipStream_t) between fork_event and join_event (two
- * hipEvent_t), i.e. underneath the tile mapper, and the rasterizer waits for it.  Everything is ordered behind `stream`
- * again when the call's work has run: buffers need no other synchronisation than for the unforked call. */
-typedef struct GsFrameFork {
-  void* side_stream;
-  void* fork_event;
-  void* join_event;
-} GsFrameFork;
-
 /* Optional per-stage timing of the frame calls: stage_events is a HOST array of 2 * GS_FWD_STAGES (gs_frame_fwd) or
  * 2 * GS_BWD_STAGES (gs_frame_bwd) hipEvent_t handles; entry 2 k is recorded in front of stage k and 2 k + 1 behind it, on
- * the stream the stage runs on; NULL entries (or a NULL array) are skipped.  This is how a caller measures one kernel's
- * launch time with HIP events on the launch stream although the whole direction is one call (bench.py's roofline). */
+ * `stream`; NULL entries (or a NULL array) are skipped.  This is how a caller measures one kernel's launch time with HIP
+ * events on the launch stream although the whole direction is one call (bench.py's roofline). */
 enum { GS_FWD_PROJECT = 0, GS_FWD_COLOURS, GS_FWD_MAP_PREPARE, GS_FWD_MAP_FINISH, GS_FWD_RASTER, GS_FWD_STAGES };
 enum { GS_BWD_RASTER = 0, GS_BWD_COLOURS, GS_BWD_PROJECT, GS_BWD_STAGES };
 
@@ -430,7 +420,7 @@ int gs_frame_layout(const GsFrame* frame, GsFrameLayout* layout);
 int gs_frame_fwd(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
                  const float* alpha_logit, const float* feature, const float* T_camera_world, const float* projection,
                  void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int32_t* counts_host,
-                 void* counts_event, const GsFrameFork* fork, void* const* stage_events, void* stream);
+                 void* counts_event, void* const* stage_events, void* stream);
 int gs_frame_bwd(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
                  const float* alpha_logit, const float* feature, const float* T_camera_world, const float* projection,
                  void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,

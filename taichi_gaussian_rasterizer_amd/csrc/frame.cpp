@@ -1,10 +1,10 @@
 // frame.cpp -- one C-ABI call per direction for a whole render_gaussians frame (reference renderer.py:134-231).
 //
-// gs_frame_fwd / gs_frame_bwd enqueue every stage of the fused frame -- the same entry points, in the same order and
-// with the same arguments as the stage-by-stage composition (taichi_gaussian_rasterizer_amd/fused.py: results are
-// bit-identical) -- from ONE host call into ONE caller-provided workspace whose sub-buffers are carved by offset
-// (gs_frame_layout).  What this removes is host time: ~25 ctypes crossings and ~20 tensor allocations per frame
-// (0.40 ms of Python per frame, the binding term for training-size images and for the ranks of a sharded frame).
+// gs_frame_fwd / gs_frame_bwd enqueue every stage of the fused frame -- the per-stage entry points of the header, in
+// the order of the composed operators (results are bit-identical) -- from ONE host call into ONE caller-provided
+// workspace whose sub-buffers are carved by offset (gs_frame_layout).  What this removes is host time: ~25 ctypes
+// crossings and ~20 tensor allocations per frame (0.40 ms of Python per frame, the binding term for training-size
+// images and for the ranks of a sharded frame).
 // Host only: no kernels here, no allocation, no synchronisation; the one event record (counts_event) lets the caller
 // wait for the mapper's counts while the sort and the rasterizer are still running.
 
@@ -142,8 +142,8 @@ extern "C" int gs_frame_layout(const GsFrame* f, GsFrameLayout* out) {
 extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
                             const float* alpha_logit, const float* feature, const float* T_camera_world,
                             const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                            int64_t scratch_bytes, int32_t* counts_host, void* counts_event, const GsFrameFork* fork,
-                            void* const* stage_events, void* stream) {
+                            int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
+                            void* stream) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
@@ -205,36 +205,17 @@ extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float
   const int32_t* v_dev = counts;
   float* colours = feats + d.col0;
   int rc;
-  // The colours are needed by the rasterizer only, and the tile mapper -- a chain of short, latency-bound launches -- does
-  // not need them: with a fork the colour kernel (HBM-bound) runs on the caller's side stream underneath the mapper and
-  // joins in front of the rasterizer.  Two event records and two stream waits, all issued from this call.
-  const bool forked = fork && fork->side_stream && fork->fork_event && fork->join_event && d.T > 0;
-  void* colour_stream = stream;
-  if (forked) {
-    if (hipEventRecord(static_cast<hipEvent_t>(fork->fork_event), s) != hipSuccess ||
-        hipStreamWaitEvent(static_cast<hipStream_t>(fork->side_stream), static_cast<hipEvent_t>(fork->fork_event), 0) !=
-            hipSuccess) {
-      gs_set_error("gs_frame_fwd: fork onto the side stream failed");
-      return GS_ERR_LAUNCH;
-    }
-    colour_stream = fork->side_stream;
-  }
-  tm.mark(GS_FWD_COLOURS, 0, colour_stream);
+  tm.mark(GS_FWD_COLOURS, 0, stream);
   if (f->sh_degree >= 0 && lists)
     rc = GS_OK;  // after the mapper's first half, on its list of touched rows (below)
   else if (f->sh_degree >= 0 && shard)
     rc = gs_sh_fwd_shard(d.n, v_dev, d.C, f->sh_degree, feature, position, indexes, cam_pos, points, f->height, cfg,
-                         shard, colours, d.F, colour_stream);
+                         shard, colours, d.F, stream);
   else if (f->sh_degree >= 0)
-    rc = gs_sh_fwd(d.n, v_dev, d.C, f->sh_degree, feature, position, indexes, cam_pos, colours, d.F, colour_stream);
+    rc = gs_sh_fwd(d.n, v_dev, d.C, f->sh_degree, feature, position, indexes, cam_pos, colours, d.F, stream);
   else
-    rc = gs_feature_gather_fwd(d.n, v_dev, d.C, feature, indexes, colours, d.F, colour_stream);
-  tm.mark(GS_FWD_COLOURS, 1, colour_stream);
-  if (forked && hipEventRecord(static_cast<hipEvent_t>(fork->join_event),
-                               static_cast<hipStream_t>(fork->side_stream)) != hipSuccess) {
-    gs_set_error("gs_frame_fwd: join event record failed");
-    return GS_ERR_LAUNCH;
-  }
+    rc = gs_feature_gather_fwd(d.n, v_dev, d.C, feature, indexes, colours, d.F, stream);
+  tm.mark(GS_FWD_COLOURS, 1, stream);
   if (rc) return rc;
   if (vis && hipMemsetAsync(vis, 0, size_t(d.n) * 4, s) != hipSuccess) {
     gs_set_error("gs_frame_fwd: hipMemsetAsync failed");
@@ -259,7 +240,7 @@ extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float
       gs_set_error("gs_frame_fwd: hipEventRecord failed");
       return GS_ERR_LAUNCH;
     }
-    return GS_OK;
+    return tm.rc;
   }
   tm.mark(GS_FWD_MAP_PREPARE, 0, stream);
   if ((rc = gs_map_prepare_ex(d.n, v_dev, points, f->width, f->height, cfg, f->k_capacity, tile_ranges, counts + 4,
@@ -293,10 +274,6 @@ extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float
                           stream)))
     return rc;
   tm.mark(GS_FWD_MAP_FINISH, 1, stream);
-  if (forked && hipStreamWaitEvent(s, static_cast<hipEvent_t>(fork->join_event), 0) != hipSuccess) {
-    gs_set_error("gs_frame_fwd: join onto the main stream failed");
-    return GS_ERR_LAUNCH;
-  }
   tm.mark(GS_FWD_RASTER, 0, stream);
   if ((rc = gs_raster_fwd(d.n, d.F, points, feats, tile_ranges, o2p, f->k_capacity, f->width, f->height, &rcfg,
                           tile_order, counts + 7, image, alpha, vis, shard, stream)))

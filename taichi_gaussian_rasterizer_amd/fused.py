@@ -8,8 +8,11 @@ on the stream with the intermediate counts (visible Gaussians V, overlaps K) lef
   * no torch glue on the path: the SH colours and the depth features are written straight into the
     rasterizer's feature rows, the rasterizer's 64-byte gradient rows are consumed in place by the SH
     and projection backward (no unpack, no cat/index backward, no zero-filled dense temporaries);
-  * the pair / overlap buffers are sized from the previous frame's K (x1.3); the mapper clamps to the
-    capacity and raises a flag, in which case the frame is re-run once with exact sizes.
+  * the whole forward is one gs_frame_fwd call into one workspace, the backward one gs_frame_bwd call (a sharded
+    frame's backward runs stage by stage: its gradient exchange sits between the rasterizer and the adjoints);
+  * the pair / overlap buffers are sized from the largest K seen for the shape (x1.25, in classes of 65 536; the first
+    frame of a shape gets the smallest class); the mapper clamps to the capacity and raises a flag, in which case the
+    frame is re-run once with room for the K it counted.
 
 This is SURVEY.md 8(f)-1: in the reference that glue is ~24 % of the forward+backward GPU time
 (profiles/bicycle_2048.txt:38,42,44,47).  Results are bit-identical to the composed operators.
@@ -26,8 +29,8 @@ from .data_types import RasterConfig
 from .spherical_harmonics import check_sh_degree
 
 _K_HINT = {}  # (n, w, h, tile_size, use_depth16) -> (max overlaps, max tile population) seen for that shape
-# True: gs_frame_fwd / gs_frame_bwd for every frame but the first of its shape; False: always the stages; "always":
-# the frame calls also for a first frame, after an untracked sizing pass (tests/conftest.py frame_path)
+# the backward of an unsharded frame: true = one gs_frame_bwd call, False = stage by stage, as a sharded frame's
+# (tests/conftest.py frame_path runs the fused-frame tests both ways)
 FRAME_CALLS = True
 _PINNED = {}  # device index -> ring of pinned int32[8] host buffers for the asynchronous count read-back
 
@@ -50,8 +53,8 @@ _EMPTY = {}    # (device, shape) -> cached empty placeholder outputs
 _FRAMES = {}   # frame key -> (GsFrame, GsFrameLayout)
 
 
-# what the stage-by-stage backward reads of its forward, by name: tensors the stages allocated, or views of the frame
-# call's workspace (points (n, 7), feats (n, F), image (h, w, F), img_depth None without render_depth, counts int32[8])
+# what the stage-by-stage backward reads of its forward, by name: views of the frame call's workspace (points (n, 7),
+# feats (n, F), image (h, w, F), img_depth None without render_depth, counts int32[8])
 _Frame = namedtuple("_Frame", "points feats slot_of indexes cam_pos tile_ranges o2p image alpha img_depth tile_order "
                               "counts")
 
@@ -97,187 +100,27 @@ def _exchange_ranks(shard, exchange, group, n, owned_range):
     return world, rank
 
 
-def _start_sparse_exchange(meta, world, rec, scratch=None, prepared=None):
-    """Bookkeeping of a sharded frame's sparse exchange, done during the FORWARD: keep the mapper's list of the splats
-    that can reach this rank's rows (M int32 rows, left in the mapper scratch) and start the all-gather of the list
-    lengths (grad_mode "sharded": of the per-owner counts, the list sorted by Gaussian index so that the entries of one
-    owner are contiguous).  The backward finds both in `meta`."""
+def _start_sparse_exchange(meta, world, touched, counts, owned_rows):
+    """Bookkeeping of a sharded frame's sparse exchange, done during the FORWARD: keep the list of the splats that can
+    reach this rank's rows, which gs_frame_fwd left in the workspace (ascending rows, so that the entries of one owner
+    are contiguous; it also evaluated the colours of exactly these rows), and start the all-gather of the list lengths
+    (grad_mode "sharded": of the per-owner counts).  The backward finds both in `meta`."""
     from . import parallel
-    n, num_tiles, M, rank = meta["n"], meta["num_tiles"], meta["touched_count"], meta["rank"]
+    M = meta["touched_count"]
     sharded = meta["grad_mode"] == "sharded"
-    if prepared is not None:  # gs_frame_fwd did it (and evaluated the colours of exactly these rows)
-        touched, counts, owned_rows = prepared
-        if not sharded:
-            counts = torch.full((1,), M, dtype=torch.int64, device=touched.device)
-    else:
-        lib = nv.lib()
-        dev = rec.indexes.device
-        # the mapper's list is grouped by screen region; ascending rows (= ascending Gaussian index) make the exchange
-        # kernels walk memory forwards and put the rows of one owner rank next to each other
-        touched = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
-        counts = torch.empty((world if sharded else 1,), dtype=torch.int64, device=dev)
-        owned_rows = torch.zeros((2,), dtype=torch.int32, device=dev) if sharded else None
-        if num_tiles > 0 and M > 0:
-            nv.check(lib.gs_map_touched_list(n, nv.ptr(rec.counts), num_tiles, nv.ptr(scratch),
-                                             lib.gs_map_scratch_bytes(n, num_tiles), nv.ptr(touched), None,
-                                             nv.ptr(rec.indexes), n, world, nv.ptr(counts) if sharded else None, rank,
-                                             nv.ptr(owned_rows), nv.stream()), "gs_map_touched_list")
-        elif sharded:
-            counts.zero_()
-        if not sharded:
-            counts.fill_(M)
-        touched = touched[:M]
+    if not sharded:
+        counts = torch.full((1,), M, dtype=torch.int64, device=touched.device)
     # a rank without tile rows or without a list has no range of rows to merge into: it merges every row
-    meta["owned_rows"] = owned_rows if (sharded and num_tiles > 0 and M > 0) else None
+    meta["owned_rows"] = owned_rows if (sharded and meta["num_tiles"] > 0 and M > 0) else None
     meta["touched"] = touched
     meta["sizes"] = parallel.SizesFuture(counts, meta["group"]) if world > 1 else None
 
 
-def _forward_stages(m, inputs, depth_range, use_depth16, render_median, key):
-    """fills the frame one C-ABI entry point per stage; returns its outputs and the record of the backward"""
-    position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
-    lib = nv.lib()
-    dev = position.device
-    n, w, full_h, C, degree, config, shard = m["n"], m["w"], m["full_h"], m["C"], m["degree"], m["config"], m["shard"]
-    render_depth = m["render_depth"]
-    # sharded frame (parallel.RowShard): everything stays in full-image coordinates; the mapper and the
-    # rasterizer skip the tile rows this rank does not own and the images hold the owned pixel rows only
-    h = full_h if shard is None else shard.local_height
-    sh = nv.make_shard(shard)
-    F = C + (2 if render_depth else 0)
-    col0 = F - C
-    cfg = nv.make_config(config)
-    # what the forward's early stop may drop is bounded by forward_cut * max|feature|: z^2 reaches far^2
-    rcfg = nv.make_config(config, cut_scale=float(depth_range[1]) ** 2) if render_depth else cfg
-    ts = config.tile_size
-    tile_shape = (-(-h // ts), -(-w // ts))
-    num_tiles = tile_shape[0] * tile_shape[1]
-    f32 = dict(dtype=torch.float32, device=dev)
-
-    points = torch.empty((n, 7), **f32)
-    depth = torch.empty((n, 1), **f32)
-    ndc = torch.empty((n, 1), **f32)
-    feats = torch.empty((n, F), **f32)
-    indexes = torch.empty((n,), dtype=torch.int64, device=dev)
-    slot_of = torch.empty((n,), dtype=torch.int32, device=dev)
-    # [0] = V (projection) ; [4:8] = K, fullest tile, overflow flag, heavy tiles (mapper scan): every word that is
-    # read is written by a kernel first, so no fill launch
-    counts = torch.empty((8,), dtype=torch.int32, device=dev)
-    cam_pos = torch.empty((3,), **f32)
-    pbytes = lib.gs_project_scratch_bytes(n)
-    pscratch = torch.empty((max(pbytes, 1),), dtype=torch.uint8, device=dev)
-    s = nv.stream()
-    nv.check(lib.gs_project_fwd(n, nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation), nv.ptr(alpha_logit),
-                                nv.ptr(T), nv.ptr(proj), w, full_h, float(depth_range[0]), float(depth_range[1]),
-                                cfg, nv.ptr(points), nv.ptr(depth), nv.ptr(ndc), nv.ptr(indexes),
-                                nv.ptr(slot_of), nv.ptr(counts), nv.ptr(feats) if render_depth else None, F,
-                                nv.ptr(cam_pos), nv.ptr(pscratch), pbytes, s), "gs_project_fwd")
-    v_dev = nv.ptr(counts)
-    if degree >= 0 and shard is not None:
-        # a rank evaluates the colours of the splats that can reach its rows only (the replicated per-Gaussian
-        # stages are what bounds the scaling of a sharded frame); the other rows get the neutral 0.5
-        nv.check(lib.gs_sh_fwd_shard(n, v_dev, C, degree, nv.ptr(feature), nv.ptr(position), nv.ptr(indexes),
-                                     nv.ptr(cam_pos), nv.ptr(points), full_h, cfg, sh,
-                                     _off(feats, col0), F, s), "gs_sh_fwd_shard")
-    elif degree >= 0:
-        nv.check(lib.gs_sh_fwd(n, v_dev, C, degree, nv.ptr(feature), nv.ptr(position), nv.ptr(indexes),
-                               nv.ptr(cam_pos), _off(feats, col0), F, s), "gs_sh_fwd")
-    else:
-        nv.check(lib.gs_feature_gather_fwd(n, v_dev, C, nv.ptr(feature), nv.ptr(indexes), _off(feats, col0), F, s),
-                 "gs_feature_gather_fwd")
-
-    tile_ranges = torch.empty((*tile_shape, 2), dtype=torch.int32, device=dev)
-    tile_order = torch.empty((num_tiles,), dtype=torch.int32, device=dev)  # heaviest tiles first
-    mbytes = lib.gs_map_scratch_bytes(n, max(num_tiles, 1))
-    mscratch = torch.empty((mbytes,), dtype=torch.uint8, device=dev)
-    want_vis = config.compute_visibility or config.compute_point_heuristic
-    hint = _K_HINT.get(key)
-    k_cap = 0 if hint is None else int(hint[0] * 1.25) + 4096
-    tile_hint = 0 if hint is None else -max(int(hint[1]), 1)  # sizing hint only; fuller tiles are still sorted
-    host_counts = _pinned_counts(dev)
-    ready = torch.cuda.Event()
-
-    def no_rows():
-        # this rank owns no tile row (more ranks than rows): nothing to map or rasterize, only V is needed
-        counts[4:8] = 0
-        host_counts[:4].copy_(counts[4:8], non_blocking=True)
-        host_counts[4:5].copy_(counts[0:1], non_blocking=True)
-        host_counts[5:6].copy_(counts[5:6], non_blocking=True)  # touched splats: none
-        ready.record()
-        return (torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0, w, F), **f32),
-                torch.empty((0, w), **f32), torch.zeros((n,), **f32) if want_vis else None)
-
-    def map_and_raster(k_cap):
-        if num_tiles == 0:
-            return no_rows()
-        nv.check(lib.gs_map_prepare(n, v_dev, nv.ptr(points), w, full_h, cfg, k_cap, nv.ptr(tile_ranges),
-                                    _off(counts, 4), nv.ptr(host_counts), nv.ptr(tile_order), sh,
-                                    nv.ptr(mscratch), mbytes, s), "gs_map_prepare")
-        # K, the overflow flag and V are final here and the scan kernel has stored them into the pinned host words
-        # itself (no copy launch): the host waits on this event while the sort and the rasterizer are still running
-        ready.record()
-        if k_cap == 0:  # first frame of this shape: K has to be known to size the buffers
-            ready.synchronize()
-            k_cap = max(int(host_counts[0]), 1)
-        o2p = torch.empty((k_cap,), dtype=torch.int32, device=dev)
-        pairs = torch.empty((k_cap,), dtype=torch.int64, device=dev)
-        nv.check(lib.gs_map_finish(n, v_dev, k_cap, tile_hint, nv.ptr(points), nv.ptr(ndc), w, full_h, cfg,
-                                   int(use_depth16),
-                                   nv.ptr(tile_ranges), nv.ptr(o2p), None, nv.ptr(pairs), sh, nv.ptr(mscratch),
-                                   mbytes, s), "gs_map_finish")
-        image = torch.empty((h, w, F), **f32)
-        alpha = torch.empty((h, w), **f32)
-        vis = torch.zeros((n,), **f32) if want_vis else None
-        nv.check(lib.gs_raster_fwd(n, F, nv.ptr(points), nv.ptr(feats), nv.ptr(tile_ranges), nv.ptr(o2p), k_cap,
-                                   w, full_h, rcfg, nv.ptr(tile_order), _off(counts, 7), nv.ptr(image),
-                                   nv.ptr(alpha), nv.ptr(vis), sh, s),
-                 "gs_raster_fwd")
-        return o2p, image, alpha, vis
-
-    o2p, image, alpha, vis = map_and_raster(k_cap)
-    ready.synchronize()  # waits for the mapper's scan only, not for the rasterizer
-    host = host_counts.tolist()
-    K, max_tile, overflow, V = host[0], host[1], host[2], host[4]  # [3] = heavy tiles, device-side only
-    if overflow:  # more overlaps than the hint allowed for: run the tail again with exact sizes
-        o2p, image, alpha, vis = map_and_raster(max(K, 1))
-        ready.synchronize()
-    _remember(key, K, max_tile)
-    m.update(V=V, K=K, h=h, F=F, col0=col0, num_tiles=num_tiles, touched_count=int(host[5]) if num_tiles > 0 else 0)
-
-    # render_depth: per-pixel epilogue (depth, depth variance, feature slice) in one pass
-    out_image, img_depth, img_var = image, None, None
-    if render_depth:
-        out_image = torch.empty((h, w, C), **f32)
-        img_depth, img_var = torch.empty((h, w), **f32), torch.empty((h, w), **f32)
-        nv.check(lib.gs_depth_split_fwd(h * w, C, nv.ptr(image), nv.ptr(alpha), 1e-6, nv.ptr(out_image),
-                                        nv.ptr(img_depth), nv.ptr(img_var), s), "gs_depth_split_fwd")
-
-    # render_median_depth: a second, non-blended forward over the same tile lists that keeps the depth of the splat
-    # taking each pixel past half opacity (reference renderer.py:203-208); no gradient
-    median = None
-    if render_median and num_tiles == 0:
-        median = torch.empty((0, w), **f32)
-    if render_median and num_tiles > 0:
-        from dataclasses import replace as _replace
-        pick = nv.make_config(_replace(config, use_alpha_blending=False, saturate_threshold=0.5,
-                                       compute_visibility=False, compute_point_heuristic=False))
-        median, covered = torch.empty((h, w), **f32), torch.empty((h, w), **f32)
-        nv.check(lib.gs_raster_fwd(n, 1, nv.ptr(points), nv.ptr(depth), nv.ptr(tile_ranges), nv.ptr(o2p),
-                                   o2p.shape[0], w, full_h, pick, nv.ptr(tile_order), _off(counts, 7),
-                                   nv.ptr(median), nv.ptr(covered), None, sh, s), "gs_raster_fwd")
-
-    outs = (out_image, alpha, points[:V], depth[:V], indexes[:V], vis[:V] if config.compute_visibility else None,
-            img_depth, img_var, median)
-    rec = _Frame(points, feats, slot_of, indexes, cam_pos, tile_ranges, o2p, image, alpha, img_depth, tile_order,
-                 counts)
-    return outs, rec, None, dict(scratch=mscratch)
-
-
 # ---------------------------------------------------------------------------------------------------------------
-# One C-ABI call per direction (include/gsplat_hip.h gs_frame_fwd / gs_frame_bwd): the same stages as
-# _forward_stages, enqueued from a single host call into one workspace whose sub-buffers are carved by offset.  Used
-# for every frame whose overlap count has been seen before (the first frame of a shape has to read K back before the
-# pair buffers can be sized: that one runs the stages, as does the re-run after a capacity overflow).
+# One C-ABI call per direction (include/gsplat_hip.h gs_frame_fwd / gs_frame_bwd): every stage of the frame, enqueued
+# from a single host call into one workspace whose sub-buffers are carved by offset.  Every frame's forward is such a
+# call, sized by the overlap count seen for its shape (none yet: the smallest class); a frame with more overlaps than
+# its capacity is run once more with room for them (render_fused).
 
 def _frame_for(n, C, degree, w, full_h, depth_range, render_depth, use_depth16, render_median, prepare_backward,
                k_cap, tile_hint, shard, config, exchange_world=0, exchange_rank=0):
@@ -320,39 +163,17 @@ def _counts_event(dev: torch.device):
     return ring["evs"][ring["at"]]
 
 
-_FORKS = {}    # device index -> (side stream, events, GsFrameFork)
-# GS_FORK_COLOURS=1: gs_frame_fwd runs the colour stage on a side stream underneath the tile mapper (GsFrameFork).
-# Measured at C3: 1.103 vs 1.108 ms per frame -- the mapper's first kernels slow down by what the overlap hides (the
-# kernel trace shows region_count at 41 us instead of 13 beside the 52-us SH kernel) -- so it is OFF by default.
-FORK_COLOURS = __import__("os").environ.get("GS_FORK_COLOURS", "0") == "1"
-
-
-def _frame_fork(dev: torch.device):
-    hit = _FORKS.get(dev.index)
-    if hit is None:
-        side = torch.cuda.Stream(device=dev)
-        evs = []
-        for _ in range(2):
-            ev = torch.cuda.Event()
-            ev.record()  # materialises the hipEvent_t
-            evs.append(ev)
-        fork = nv.GsFrameFork(side.cuda_stream, evs[0].cuda_event, evs[1].cuda_event)
-        hit = _FORKS[dev.index] = (side, evs, fork)
-    return ctypes.byref(hit[2])
-
-
 def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median, key, k_cap, tile_hint, world,
                   rank):
     """fills the frame by one gs_frame_fwd call into a workspace sized for k_cap overlaps (raises _Overflow when the
-    frame has more); returns its outputs, the record of a stage-by-stage backward (None when gs_frame_bwd takes the
-    backward, or when there is none) and the workspace"""
+    frame has more); returns its outputs, the workspace and, for a sparse exchange, the lists gs_frame_fwd prepared"""
     position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
     lib = nv.lib()
     dev = position.device
     n, w, full_h, C, config, shard = m["n"], m["w"], m["full_h"], m["C"], m["config"], m["shard"]
     render_depth = m["render_depth"]
     # a sharded frame's backward runs stage by stage (the exchange sits in its middle) and clears its own rows
-    prepare_backward = needs_grad and shard is None
+    prepare_backward = needs_grad and shard is None and bool(FRAME_CALLS)
     frame, L = _frame_for(n, C, m["degree"], w, full_h, depth_range, render_depth, use_depth16, render_median,
                           prepare_backward, k_cap, tile_hint, shard, config, world, rank)
     ws = torch.empty((L.workspace_bytes,), dtype=torch.uint8, device=dev)
@@ -362,48 +183,52 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
     nv.check(lib.gs_frame_fwd(ctypes.byref(frame), nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation),
                               nv.ptr(alpha_logit), nv.ptr(feature), nv.ptr(T), nv.ptr(proj), nv.ptr(ws),
                               L.workspace_bytes, nv.ptr(scratch), L.fwd_scratch_bytes, nv.ptr(host_counts),
-                              ready_handle, _frame_fork(dev) if FORK_COLOURS else None,
-                              nv.stage_events(nv.FRAME_FWD_STAGES), nv.stream()), "gs_frame_fwd")
+                              ready_handle, nv.stage_events(nv.FRAME_FWD_STAGES), nv.stream()), "gs_frame_fwd")
     ready.synchronize()  # waits for the mapper's scan only, not for the rasterizer
     host = host_counts.tolist()
     K, max_tile, overflow, V = host[0], host[1], host[2], host[4]
     _remember(key, K, max_tile)
-    if overflow:  # more overlaps than the hint allowed for: the caller runs the frame again with exact sizes
+    if overflow:  # more overlaps than the capacity: the caller runs the frame again, sized for the K just recorded
         raise _Overflow()
 
     F, h = L.num_features, L.local_height
     num_tiles = max(L.tiles_x * L.tiles_y, 0)
     M = int(host[5]) if num_tiles > 0 else 0
-    m.update(V=V, K=K, h=h, F=F, col0=F - C, num_tiles=num_tiles, touched_count=M)
-    if prepare_backward:
-        m["frame"], m["rows_clean"] = (frame, L), True
+    # rows_clean: gs_frame_fwd has zero-filled the gradient rows gs_frame_bwd accumulates into
+    m.update(V=V, K=K, h=h, F=F, col0=F - C, num_tiles=num_tiles, touched_count=M, frame=(frame, L),
+             rows_clean=prepare_backward)
     f32, i32, i64 = ws.view(torch.float32), ws.view(torch.int32), ws.view(torch.int64)
-    image, alpha = _carve(f32, L.image, (h, w, F)), _carve(f32, L.alpha, (h, w))
-    img_depth = _carve(f32, L.img_depth, (h, w)) if render_depth else None
-    outs = (_carve(f32, L.out_image, (h, w, C)) if render_depth else image, alpha, _carve(f32, L.points, (V, 7)),
-            _carve(f32, L.depth, (V, 1)), _carve(i64, L.indexes, (V,)),
-            _carve(f32, L.visibility, (V,)) if config.compute_visibility else None, img_depth,
+    image = _carve(f32, L.image, (h, w, F))
+    outs = (_carve(f32, L.out_image, (h, w, C)) if render_depth else image, _carve(f32, L.alpha, (h, w)),
+            _carve(f32, L.points, (V, 7)), _carve(f32, L.depth, (V, 1)), _carve(i64, L.indexes, (V,)),
+            _carve(f32, L.visibility, (V,)) if config.compute_visibility else None,
+            _carve(f32, L.img_depth, (h, w)) if render_depth else None,
             _carve(f32, L.img_var, (h, w)) if render_depth else None,
             _carve(f32, L.median, (h, w)) if render_median else None)
-    rec = None
-    if needs_grad and not prepare_backward:
-        rec = _Frame(_carve(f32, L.points, (n, 7)), _carve(f32, L.features, (n, F)), _carve(i32, L.slot_of, (n,)),
-                     _carve(i64, L.indexes, (n,)), _carve(f32, L.camera_pos, (3,)),
-                     _carve(i32, L.tile_ranges, (num_tiles, 2)), _carve(i32, L.overlap_to_point, (k_cap,)), image,
-                     alpha, img_depth, _carve(i32, L.tile_order, (num_tiles,)), _carve(i32, L.counts, (8,)))
-    ex = None
+    lists = None
     if shard is not None and m["exchange"] == "sparse":
         # the frame call has already compacted the list (ascending rows) and cut it by owner; owned_rows = counts[2:4]
-        ex = dict(prepared=(_carve(i32, L.touched, (M,)), _carve(i64, L.owner_counts, (world,)),
-                            _carve(i32, L.counts + 8, (2,))))
-    return outs, rec, ws, ex
+        lists = (_carve(i32, L.touched, (M,)), _carve(i64, L.owner_counts, (world,)), _carve(i32, L.counts + 8, (2,)))
+    return outs, ws, lists
+
+
+def _record(m, ws):
+    """the _Frame the stage-by-stage backward reads: views of the frame call's workspace"""
+    frame, L = m["frame"]
+    n, w, h, F, num_tiles = m["n"], m["w"], m["h"], m["F"], m["num_tiles"]
+    f32, i32, i64 = ws.view(torch.float32), ws.view(torch.int32), ws.view(torch.int64)
+    return _Frame(_carve(f32, L.points, (n, 7)), _carve(f32, L.features, (n, F)), _carve(i32, L.slot_of, (n,)),
+                  _carve(i64, L.indexes, (n,)), _carve(f32, L.camera_pos, (3,)),
+                  _carve(i32, L.tile_ranges, (num_tiles, 2)), _carve(i32, L.overlap_to_point, (frame.k_capacity,)),
+                  _carve(f32, L.image, (h, w, F)), _carve(f32, L.alpha, (h, w)),
+                  _carve(f32, L.img_depth, (h, w)) if m["render_depth"] else None,
+                  _carve(i32, L.tile_order, (num_tiles,)), _carve(i32, L.counts, (8,)))
 
 
 def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, image_size,
              depth_range, config: RasterConfig, render_depth: bool, use_depth16: bool, render_median: bool, shard,
              group, holder, exchange: str, grad_mode: str, owned_range, key, k_cap: int, tile_hint: int):
-    """the forward of the frame node; `needs`: which of the seven tensors get a gradient.  k_cap == 0: stage by stage,
-    else one gs_frame_fwd call"""
+    """the forward of the frame node; `needs`: which of the seven tensors get a gradient"""
     nv.require_device(position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
                       what="render_gaussians")
     inputs = (position, log_scaling, rotation, alpha_logit, feature, T_camera_world.contiguous(),
@@ -414,20 +239,17 @@ def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, 
     m = dict(n=n, w=int(image_size[0]), full_h=int(image_size[1]), C=feature.shape[1],
              degree=check_sh_degree(feature) if feature.dim() == 3 else -1,  # -1: plain (N, C) features, no SH
              config=config, render_depth=render_depth, group=group, shard=shard, exchange=exchange,
-             grad_mode=grad_mode, owned_range=owned_range, rank=rank, frame=None)
-    if k_cap:
-        outs, rec, ws, ex = _forward_call(m, inputs, any(needs), depth_range, use_depth16, render_median, key, k_cap,
-                                          tile_hint, world, rank)
-    else:
-        outs, rec, ws, ex = _forward_stages(m, inputs, depth_range, use_depth16, render_median, key)
+             grad_mode=grad_mode, owned_range=owned_range, rank=rank)
+    outs, ws, lists = _forward_call(m, inputs, any(needs), depth_range, use_depth16, render_median, key, k_cap,
+                                    tile_hint, world, rank)
     out_image, alpha, points_v, depth_v, indexes_v, vis_out, img_depth, img_var, median = outs
 
     vis_out, img_depth, img_var, median = (_empty(dev, (0,)) if t is None else t
                                            for t in (vis_out, img_depth, img_var, median))
     heur = torch.zeros((m["V"], 2), dtype=torch.float32, device=dev) if config.compute_point_heuristic \
         else _empty(dev, (0, 2))
-    if shard is not None and exchange == "sparse":
-        _start_sparse_exchange(m, world, rec, **ex)
+    if lists is not None:
+        _start_sparse_exchange(m, world, *lists)
     if holder is not None and shard is not None:
         holder["touched_count"] = m["touched_count"]
     ctx.meta = m
@@ -436,7 +258,7 @@ def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, 
     ctx.holder = holder
     # outputs nobody differentiates through (projected splats, depths) must not cost zero-filled gradients
     ctx.set_materialize_grads(False)
-    ctx.save_for_backward(*inputs, *(rec if rec is not None else (ws,)))
+    ctx.save_for_backward(*inputs, ws)
     ctx.mark_non_differentiable(alpha, indexes_v, vis_out, heur, median)
     if not render_depth:
         ctx.mark_non_differentiable(img_depth, img_var)
@@ -678,12 +500,13 @@ class _FrameRender(torch.autograd.Function):
     @nv.on_tensor_device
     def backward(ctx, g_image, _g_alpha, g_points, g_depth, _g_idx, _g_vis, _g_heur, g_img_depth, g_img_var,
                  _g_median=None):
-        # gs_frame_bwd for a frame whose gs_frame_fwd prepared it, else stage by stage
+        # gs_frame_bwd for a frame whose gs_frame_fwd prepared it, else stage by stage on views of the workspace
         saved = ctx.saved_tensors
-        if ctx.meta["frame"] is not None:
-            d = _backward_call(ctx, saved[:7], saved[7], g_image, g_points, g_depth, g_img_depth, g_img_var)
+        inputs, ws = saved[:7], saved[7]
+        if ctx.meta["frame"][0].prepare_backward:
+            d = _backward_call(ctx, inputs, ws, g_image, g_points, g_depth, g_img_depth, g_img_var)
         else:
-            d = _backward_stages(ctx, saved[:7], _Frame(*saved[7:]), g_image, g_points, g_depth, g_img_depth,
+            d = _backward_stages(ctx, inputs, _record(ctx.meta, ws), g_image, g_points, g_depth, g_img_depth,
                                  g_img_var)
         return d + (None,) * (len(ctx.needs_input_grad) - len(d))
 
@@ -742,11 +565,6 @@ def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: b
             use_depth16, render_median_depth, shard, group, holder, exchange, grad_mode, owned_range)
     size = camera_params.image_size
     key = (args[0].shape[0], int(size[0]), int(size[1]), shard, config.tile_size, bool(use_depth16))
-    hint = _K_HINT.get(key)
-    if hint is None and FRAME_CALLS == "always":  # tests: size the frame by an untracked staged pass first
-        with torch.no_grad():
-            _FrameRender.apply(*args[:16], "dense", "replicated", None, key, 0, 0)
-        hint = _K_HINT.get(key)
     if owned is not None:
         # grad_mode "sharded": gradients flow to the rank's own rows (range-shaped leaf tensors), see _OwnedRender
         own = (owned.position.contiguous(), owned.log_scaling.contiguous(), owned.rotation.contiguous(),
@@ -758,10 +576,20 @@ def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: b
     else:
         def render(*sizes):
             return _FrameRender.apply(*args, key, *sizes)
+    # a shape seen for the first time gets the smallest capacity class
+    outs = None
     try:
-        outs = render(*(_capacity(hint) if hint is not None and FRAME_CALLS else (0, 0)))
-    except _Overflow:  # more overlaps than the hint allowed for (now updated): run the stages with exact sizes
-        outs = render(0, 0)
+        outs = render(*_capacity(_K_HINT.get(key, (0, 0))))
+    except _Overflow:  # more overlaps than the capacity: K is recorded now
+        pass
+    if outs is None:
+        # run again outside the except block, whose traceback still holds the failed attempt's workspace; the mapper
+        # is deterministic, so the same frame at a capacity of at least its K cannot overflow again
+        try:
+            outs = render(*_capacity(_K_HINT[key]))
+        except _Overflow:
+            raise RuntimeError(f"render_gaussians: the re-run of an overflowing frame overflowed again (hint "
+                               f"{_K_HINT[key]})") from None
     image, alpha, g2d, depths, indexes, vis, heur, img_depth, img_var, median = outs
     holder["gaussians2d"] = weakref.ref(g2d)
     indexes._gs_unique = True

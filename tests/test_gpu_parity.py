@@ -1039,16 +1039,24 @@ def test_fused_frame_splits_heavy_tiles(nb, monkeypatch, frame_path):
         pu.assert_grad_close(t.grad, getattr(b, k).grad, f"grad {k} with split tiles", tol=1e-3)
 
 
-def test_fused_frame_capacity_overflow_rerun():
+@pytest.mark.parametrize("n,first_frame", [(8000, False), (30000, True)], ids=["poisoned_hint", "first_frame"])
+def test_fused_frame_capacity_overflow_rerun(n, first_frame):
+    """first_frame: a shape without a hint starts at the smallest capacity class (65 536 overlaps); this scene has more,
+    so its first frame is the re-run after an overflow, and it must give the bits of a later frame with a warm hint"""
     from taichi_gaussian_rasterizer_amd import fused
-    size, n = (256, 192), 8000
+    size = (256, 192)
     cfg = RasterConfig()
     g, camera = scenes.benchmark_scene(n, size, sh_degree=1, seed=0)
     cam = camera.to(device=DEV)
+    if first_frame:
+        fused._K_HINT.clear()
     ref = gs.render_gaussians(g.to(DEV), cam, cfg, use_sh=True)
     key = next(iter(k for k in fused._K_HINT if k[0] == n and k[1] == size[0]))
     true_k, true_max = fused._K_HINT[key]
-    fused._K_HINT[key] = (true_k // 3, 8)  # poison the hints: the frame must detect the overflow and re-run,
+    if first_frame:
+        assert true_k > 65536
+    else:
+        fused._K_HINT[key] = (true_k // 3, 8)  # poison the hints: the frame must detect the overflow and re-run,
     again = gs.render_gaussians(g.to(DEV), cam, cfg, use_sh=True)  # and the catch-all sort must cover fuller tiles
     assert torch.equal(again.image, ref.image) and fused._K_HINT[key][0] == true_k
 

@@ -98,7 +98,7 @@ def _run_modes(rank, world, port, size, n, depth_mode, interleave, grad_mode, fr
         else:
             g = g.requires_grad_(True)
         holder = owned if owned is not None else g
-        for _ in range(frames):  # the second frame of a shape goes through gs_frame_fwd (one call for the forward)
+        for _ in range(frames):  # the second frame of a shape is sized by the overlap count of the first
             for _, t in holder.items():
                 t.grad = None
             r = parallel.render_gaussians_sharded(g, cam, RasterConfig(), use_sh=True, render_depth=depth_mode,
@@ -118,12 +118,13 @@ def _run_modes(rank, world, port, size, n, depth_mode, interleave, grad_mode, fr
     (False, 0, 2, (320, 256), "replicated"), (True, 2, 3, (320, 250), "replicated"),
     (True, 0, 3, (320, 30), "replicated"),            # rank 2 owns no tile row: an empty list
     (False, 0, 2, (320, 256), "sharded"), (True, 3, 3, (320, 250), "sharded"),
-    (True, 0, 3, (320, 30), "sharded")])              # the rowless rank through the stages, then gs_frame_fwd
+    (True, 0, 3, (320, 30), "sharded")])              # rank 2 owns no tile row: no range of rows to merge into
 def test_fused_sharded_frame_sparse_exchange(tmp_path, depth_mode, interleave, world, size, grad_mode):
     """the fused frame's sparse exchange under a real process group (gloo ranks sharing the GPU): lists of the touched
     splats instead of dense rows; "replicated": every rank ends with the single-process gradients and all ranks with the
     SAME bits; "sharded": rank r ends with the complete gradients of its own index range, range-shaped, through one
-    all-to-all and adjoints that run on that range only.  Two frames: staged forward, then gs_frame_fwd."""
+    all-to-all and adjoints that run on that range only.  Two frames: the first of its shape, then one sized by the
+    overlap count the first recorded."""
     import taichi_gaussian_rasterizer_amd as gs
     from taichi_gaussian_rasterizer_amd import RasterConfig, parallel
     n = 20000
