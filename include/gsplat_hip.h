@@ -372,8 +372,13 @@ int gs_depth_split_bwd(int64_t pixels, int32_t channels, const float* depth, con
  *     attached to the projected splats / depths themselves (optional).  Outputs: dense parameter gradients
  *     d_position (n,3), d_log_scaling (n,3), d_rotation (n,4), d_alpha_logit (n,1), d_feature (n,C[,D]);
  *     d_T_camera_world (16) / d_projection (4) optional; d_camera_centre (3, optional, ZEROED BY THE CALLER) receives
- *     the SH view direction's gradient with respect to the camera centre.  Not for sharded frames (their backward
- *     exchanges partial gradients between the rasterizer and the per-Gaussian adjoints: run the stages).
+ *     the SH view direction's gradient with respect to the camera centre.
+ *   gs_frame_bwd_part: gs_frame_bwd with a trailing `part` (GsFrameBwdPart; NULL = gs_frame_bwd): run the stages
+ *     [first_stage, end_stage) of GS_BWD_* only -- RASTER (clears the gradient rows unless prepare_backward did),
+ *     COLOURS (SH / feature-gather adjoint from colour_grads), PROJECT (adds the attached gradients into splat_grads,
+ *     then the projection adjoint) -- on the Gaussians [row_begin, row_end), whose gradients fill outputs of
+ *     row_end - row_begin rows.  A sharded frame exchanges its partial gradients between RASTER and COLOURS, so no
+ *     call of it may run both (gs_frame_bwd, which runs every stage, refuses sharded frames).
  */
 typedef struct GsFrame {
   int64_t n;
@@ -410,11 +415,19 @@ typedef struct GsFrameLayout {
 } GsFrameLayout;
 
 /* Optional per-stage timing of the frame calls: stage_events is a HOST array of 2 * GS_FWD_STAGES (gs_frame_fwd) or
- * 2 * GS_BWD_STAGES (gs_frame_bwd) hipEvent_t handles; entry 2 k is recorded in front of stage k and 2 k + 1 behind it, on
+ * 2 * GS_BWD_STAGES (gs_frame_bwd[_part]) hipEvent_t handles; entry 2 k is recorded in front of stage k and 2 k + 1 behind it, on
  * `stream`; NULL entries (or a NULL array) are skipped.  This is how a caller measures one kernel's launch time with HIP
  * events on the launch stream although the whole direction is one call (bench.py's roofline). */
 enum { GS_FWD_PROJECT = 0, GS_FWD_COLOURS, GS_FWD_MAP_PREPARE, GS_FWD_MAP_FINISH, GS_FWD_RASTER, GS_FWD_STAGES };
 enum { GS_BWD_RASTER = 0, GS_BWD_COLOURS, GS_BWD_PROJECT, GS_BWD_STAGES };
+
+typedef struct GsFrameBwdPart {
+  int32_t first_stage, end_stage;  /* GS_BWD_* */
+  const float* colour_grads;       /* NULL: the gradient rows' colour columns (7 + F - channels, row stride RS) */
+  float* splat_grads;              /* NULL: the gradient rows (splat columns 0..6, depth features 7..8) */
+  int32_t colour_stride, splat_stride;
+  int64_t row_begin, row_end;
+} GsFrameBwdPart;
 
 int gs_frame_layout(const GsFrame* frame, GsFrameLayout* layout);
 int gs_frame_fwd(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
@@ -428,6 +441,14 @@ int gs_frame_bwd(const GsFrame* frame, const float* position, const float* log_s
                  const float* attached_points, const float* attached_depth, float* d_position, float* d_log_scaling,
                  float* d_rotation, float* d_alpha_logit, float* d_feature, float* d_T_camera_world,
                  float* d_projection, float* d_camera_centre, void* const* stage_events, void* stream);
+int gs_frame_bwd_part(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
+                      const float* alpha_logit, const float* feature, const float* T_camera_world,
+                      const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                      int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image, const float* grad_img_depth,
+                      const float* grad_img_var, const float* attached_points, const float* attached_depth,
+                      float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
+                      float* d_feature, float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                      void* const* stage_events, void* stream, const GsFrameBwdPart* part);
 
 /* ------------------------------------------------------------------- Morton ordering --
  * replaces: misc/morton_sort.py:78-88 code_points64_kernel (Grid.morton_code64, :37-66).  points (n,3);

@@ -55,6 +55,14 @@ class GsFrameLayout(ctypes.Structure):
         ("local_height", c_int32)]
 
 
+class GsFrameBwdPart(ctypes.Structure):
+    """include/gsplat_hip.h GsFrameBwdPart: the stages and Gaussian rows one gs_frame_bwd_part call runs, and where its
+    adjoints read the colour / splat gradients (NULL = the frame's gradient rows)"""
+    _fields_ = [("first_stage", c_int32), ("end_stage", c_int32), ("colour_grads", c_void_p),
+                ("splat_grads", c_void_p), ("colour_stride", c_int32), ("splat_stride", c_int32),
+                ("row_begin", c_int64), ("row_end", c_int64)]
+
+
 # Developer tuning aids (tools/exp_*.py, the wave-region tests): passed per call inside GsRasterConfig; the
 # library itself reads no environment variable.  GS_RASTER_NB / GS_RASTER_HEAVY seed them at import.
 TUNING = {"wave_sub_blocks": int(os.environ.get("GS_RASTER_NB", "0") or 0),
@@ -120,6 +128,8 @@ SIGNATURES = {
     "gs_frame_fwd": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P]),
     "gs_frame_bwd": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P,
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_frame_bwd_part": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
+                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(GsFrameBwdPart)]),
 }
 
 _lib = None
@@ -148,17 +158,19 @@ timer = KernelTimer()
 # they stand for, so that bench.py's per-stage table and byte formulas read the same either way
 FRAME_FWD_STAGES = ("gs_project_fwd", "gs_sh_fwd", "gs_map_prepare", "gs_map_finish", "gs_raster_fwd")
 FRAME_BWD_STAGES = ("gs_raster_bwd", "gs_sh_bwd", "gs_project_bwd")
+GS_BWD_RASTER, GS_BWD_COLOURS, GS_BWD_PROJECT, GS_BWD_STAGES = range(4)
 
 
-def stage_events(names):
-    """None, or a ctypes array of hipEvent_t pairs for the stages of a frame call that `timer` is asked to time; the
-    (start, stop) torch events are filed under the stage names in `timer.records`."""
+def stage_events(names, run=None):
+    """None, or a ctypes array of hipEvent_t pairs for the stages of a frame call that `timer` is asked to time (of the
+    stage numbers in `run` only, if given: the stages the call runs); the (start, stop) torch events are filed under
+    the stage names in `timer.records`."""
     if not timer.enabled:
         return None
     arr = (c_void_p * (2 * len(names)))()
     used = False
     for k, name in enumerate(names):
-        if timer.only is not None and name not in timer.only:
+        if (timer.only is not None and name not in timer.only) or (run is not None and k not in run):
             continue
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
@@ -179,7 +191,8 @@ class _TimedLib:
     def __getattr__(self, name):  # first lookup only: the result is stored on the instance
         fn = getattr(self._h, name)
         if name.endswith("_bytes") or name in ("gs_last_error", "gs_version", "gs_grad_row_floats", "gs_frame_layout",
-                                               "gs_frame_fwd", "gs_frame_bwd", "gs_map_touched_offset"):
+                                               "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_part",
+                                               "gs_map_touched_offset"):
             setattr(self, name, fn)
             return fn
 

@@ -299,25 +299,29 @@ extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float
   return tm.rc;
 }
 
-int gs_rows_add(int64_t v, int32_t row_floats, float* rows, const float* add_points, const float* add_depth,
-                int32_t depth_col, void* stream);
-
-extern "C" int gs_frame_bwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
-                            const float* alpha_logit, const float* feature, const float* T_camera_world,
-                            const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                            int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
-                            const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
-                            const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
-                            float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
-                            float* d_camera_centre, void* const* stage_events, void* stream) {
+extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const float* log_scaling,
+                                 const float* rotation, const float* alpha_logit, const float* feature,
+                                 const float* T_camera_world, const float* projection, void* workspace,
+                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
+                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+                                 const float* attached_points, const float* attached_depth, float* d_position,
+                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
   GsFrameLayout L;
   if (int rc = gs_frame_layout(f, &L)) return rc;
-  GS_REQUIRE(!f->has_shard, GS_ERR_UNSUPPORTED,
-             "gs_frame_bwd: a sharded frame exchanges its partial gradients between the two halves of the backward; "
-             "run the stages (gs_raster_bwd, gs_shard_pack_grads, gs_sh_bwd, gs_project_bwd)");
+  const int first = part ? part->first_stage : GS_BWD_RASTER, end = part ? part->end_stage : GS_BWD_STAGES;
+  const int64_t lo = part ? part->row_begin : 0, nr = (part ? part->row_end : d.n) - lo;
+  GS_REQUIRE(first >= 0 && first < end && end <= GS_BWD_STAGES, GS_ERR_INVALID_ARGUMENT,
+             "gs_frame_bwd: stages [%d, %d)", first, end);
+  GS_REQUIRE(lo >= 0 && nr >= 0 && lo + nr <= d.n, GS_ERR_INVALID_ARGUMENT, "gs_frame_bwd: rows [%lld, %lld) of %lld",
+             (long long)lo, (long long)(lo + nr), (long long)d.n);
+  GS_REQUIRE(!f->has_shard || first > GS_BWD_RASTER || end <= GS_BWD_COLOURS, GS_ERR_UNSUPPORTED,
+             "gs_frame_bwd: a sharded frame exchanges its partial gradients between the rasterizer and the adjoints; "
+             "run [GS_BWD_RASTER, GS_BWD_COLOURS) and the later stages in separate calls");
   GS_REQUIRE(workspace && workspace_bytes >= L.workspace_bytes, GS_ERR_SCRATCH_TOO_SMALL,
              "gs_frame_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.workspace_bytes);
   GS_REQUIRE(scratch && scratch_bytes >= L.bwd_scratch_bytes, GS_ERR_SCRATCH_TOO_SMALL,
@@ -329,58 +333,81 @@ extern "C" int gs_frame_bwd(const GsFrame* f, const float* position, const float
   hipStream_t s = static_cast<hipStream_t>(stream);
   const GsRasterConfig* cfg = &f->cfg;
   const int32_t* counts = at<int32_t>(workspace, L.counts);
-  const float* cam_pos = at<float>(workspace, L.camera_pos);
-  const float* points = at<float>(workspace, L.points);
   const float* feats = at<float>(workspace, L.features);
-  const int64_t* indexes = at<int64_t>(workspace, L.indexes);
-  const int32_t* slot_of = at<int32_t>(workspace, L.slot_of);
+  const int32_t* slot_of = at<int32_t>(workspace, L.slot_of) + lo;  // the adjoints run on the rows [lo, lo + nr)
   float* rows = L.grad_rows >= 0 ? at<float>(workspace, L.grad_rows) : at<float>(scratch, L.b_grad_rows);
-  if (L.grad_rows < 0 && v > 0 && hipMemsetAsync(rows, 0, size_t(v) * d.RS * 4, s) != hipSuccess) {
-    gs_set_error("gs_frame_bwd: hipMemsetAsync failed");
-    return GS_ERR_LAUNCH;
-  }
+  const bool own_colours = part && part->colour_grads, own_splats = part && part->splat_grads;
+  const float* colours = own_colours ? part->colour_grads : rows + 7 + d.col0;
+  float* splats = own_splats ? part->splat_grads : rows;
+  const int32_t colour_stride = own_colours ? part->colour_stride : d.RS;
+  const int32_t splat_stride = own_splats ? part->splat_stride : d.RS;
   int rc;
-  const float* g_img = grad_image;
-  if (f->render_depth && v > 0 && d.P > 0 && (grad_image || grad_img_depth || grad_img_var)) {
-    // assemble the gradient of the rasterized (H, W, 2 + C) image from the three upstream gradients
-    float* assembled = at<float>(scratch, L.b_grad_image);
-    if ((rc = gs_depth_split_bwd(d.P, d.C, at<float>(workspace, L.img_depth), at<float>(workspace, L.alpha), 1e-6f,
-                                 grad_image, grad_img_depth, grad_img_var, assembled, stream)))
+  if (first <= GS_BWD_RASTER) {
+    if (L.grad_rows < 0 && v > 0 && hipMemsetAsync(rows, 0, size_t(v) * d.RS * 4, s) != hipSuccess) {
+      gs_set_error("gs_frame_bwd: hipMemsetAsync failed");
+      return GS_ERR_LAUNCH;
+    }
+    const float* g_img = grad_image;
+    if (f->render_depth && v > 0 && d.P > 0 && (grad_image || grad_img_depth || grad_img_var)) {
+      // assemble the gradient of the rasterized (H, W, 2 + C) image from the three upstream gradients
+      float* assembled = at<float>(scratch, L.b_grad_image);
+      if ((rc = gs_depth_split_bwd(d.P, d.C, at<float>(workspace, L.img_depth), at<float>(workspace, L.alpha), 1e-6f,
+                                   grad_image, grad_img_depth, grad_img_var, assembled, stream)))
+        return rc;
+      g_img = assembled;
+    }
+    tm.mark(GS_BWD_RASTER, 0, stream);
+    if (g_img && v > 0 && d.P > 0 && k > 0 &&
+        (rc = gs_raster_bwd(v, d.F, at<float>(workspace, L.points), feats, at<int32_t>(workspace, L.tile_ranges),
+                            at<int32_t>(workspace, L.overlap_to_point), k, f->width, f->height, cfg,
+                            at<int32_t>(workspace, L.tile_order), counts + 7, at<float>(workspace, L.image), g_img,
+                            rows, f->has_shard ? &f->shard : nullptr, stream)))
       return rc;
-    g_img = assembled;
+    tm.mark(GS_BWD_RASTER, 1, stream);
   }
-  tm.mark(GS_BWD_RASTER, 0, stream);
-  if (g_img && v > 0 && d.P > 0 && k > 0 &&
-      (rc = gs_raster_bwd(v, d.F, points, feats, at<int32_t>(workspace, L.tile_ranges),
-                          at<int32_t>(workspace, L.overlap_to_point), k, f->width, f->height, cfg,
-                          at<int32_t>(workspace, L.tile_order), counts + 7, at<float>(workspace, L.image), g_img, rows,
-                          nullptr, stream)))
-    return rc;
-  tm.mark(GS_BWD_RASTER, 1, stream);
-  // gradients a caller attached to the projected splats / depths themselves (e.g. a regulariser)
-  const float* extra_depth = nullptr;
-  if (v > 0 && (attached_points || (attached_depth && f->render_depth))) {
-    if ((rc = gs_rows_add(v, d.RS, rows, attached_points, f->render_depth ? attached_depth : nullptr, 7, stream)))
+  if (first <= GS_BWD_COLOURS && end > GS_BWD_COLOURS) {
+    tm.mark(GS_BWD_COLOURS, 0, stream);
+    if (f->sh_degree >= 0)
+      rc = gs_sh_bwd(nr, v, d.C, f->sh_degree, feature + lo * d.C * d.D, position + 3 * lo,
+                     at<int64_t>(workspace, L.indexes), 1, slot_of, at<float>(workspace, L.camera_pos), colours,
+                     colour_stride, feats + d.col0, d.F, d_feature, nullptr, d_camera_centre, stream);
+    else
+      rc = gs_feature_gather_bwd(nr, d.C, slot_of, colours, colour_stride, d_feature, stream);
+    tm.mark(GS_BWD_COLOURS, 1, stream);
+    if (rc) return rc;
+  }
+  if (end > GS_BWD_PROJECT) {
+    // gradients a caller attached to the projected splats / depths themselves (e.g. a regulariser); the colour adjoint
+    // never reads these columns, and a sharded frame adds them after its exchange: every rank holds the same, whole ones
+    if ((rc = gs_rows_add(v, splat_stride, splats, attached_points, f->render_depth ? attached_depth : nullptr, 7,
+                          stream)))
       return rc;
+    const bool camera = d_T_camera_world || d_projection;
+    const float* gd = f->render_depth ? splats + 7 : (v > 0 ? attached_depth : nullptr);
+    tm.mark(GS_BWD_PROJECT, 0, stream);
+    rc = gs_project_bwd(nr, v, position + 3 * lo, log_scaling + 3 * lo, rotation + 4 * lo, alpha_logit + lo,
+                        T_camera_world, projection, f->width, f->height, cfg, slot_of, splats, splat_stride, gd,
+                        f->render_depth ? splats + 8 : nullptr, f->render_depth ? splat_stride : 1, d_position,
+                        d_log_scaling, d_rotation, d_alpha_logit, d_T_camera_world, d_projection,
+                        camera ? at<char>(scratch, L.b_camera) : nullptr,
+                        camera ? gs_project_bwd_scratch_bytes(nr) : 0, stream);
+    tm.mark(GS_BWD_PROJECT, 1, stream);
+    if (rc) return rc;
   }
-  if (attached_depth && v > 0 && !f->render_depth) extra_depth = attached_depth;
-  tm.mark(GS_BWD_COLOURS, 0, stream);
-  if (f->sh_degree >= 0)
-    rc = gs_sh_bwd(d.n, v, d.C, f->sh_degree, feature, position, indexes, 1, slot_of, cam_pos, rows + 7 + d.col0, d.RS,
-                   feats + d.col0, d.F, d_feature, nullptr, d_camera_centre, stream);
-  else
-    rc = gs_feature_gather_bwd(d.n, d.C, slot_of, rows + 7 + d.col0, d.RS, d_feature, stream);
-  tm.mark(GS_BWD_COLOURS, 1, stream);
-  if (rc) return rc;
-  const bool camera = d_T_camera_world || d_projection;
-  const float* gd = f->render_depth ? rows + 7 : extra_depth;
-  const float* gd2 = f->render_depth ? rows + 8 : nullptr;
-  tm.mark(GS_BWD_PROJECT, 0, stream);
-  rc = gs_project_bwd(d.n, v, position, log_scaling, rotation, alpha_logit, T_camera_world, projection, f->width,
-                      f->height, cfg, slot_of, rows, d.RS, gd, gd2, f->render_depth ? d.RS : 1, d_position,
-                      d_log_scaling, d_rotation, d_alpha_logit, d_T_camera_world, d_projection,
-                      camera ? at<char>(scratch, L.b_camera) : nullptr,
-                      camera ? gs_project_bwd_scratch_bytes(d.n) : 0, stream);
-  tm.mark(GS_BWD_PROJECT, 1, stream);
-  return rc ? rc : tm.rc;
+  return tm.rc;
+}
+
+extern "C" int gs_frame_bwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
+                            const float* alpha_logit, const float* feature, const float* T_camera_world,
+                            const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                            int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
+                            const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
+                            const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
+                            float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
+                            float* d_camera_centre, void* const* stage_events, void* stream) {
+  return gs_frame_bwd_part(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
+                           workspace, workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth,
+                           grad_img_var, attached_points, attached_depth, d_position, d_log_scaling, d_rotation,
+                           d_alpha_logit, d_feature, d_T_camera_world, d_projection, d_camera_centre, stage_events,
+                           stream, nullptr);
 }

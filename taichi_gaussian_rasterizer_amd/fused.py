@@ -9,7 +9,7 @@ on the stream with the intermediate counts (visible Gaussians V, overlaps K) lef
     rasterizer's feature rows, the rasterizer's 64-byte gradient rows are consumed in place by the SH
     and projection backward (no unpack, no cat/index backward, no zero-filled dense temporaries);
   * the whole forward is one gs_frame_fwd call into one workspace, the backward one gs_frame_bwd call (a sharded
-    frame's backward runs stage by stage: its gradient exchange sits between the rasterizer and the adjoints);
+    frame's backward is three: its gradient exchange sits between the rasterizer and the adjoints);
   * the pair / overlap buffers are sized from the largest K seen for the shape (x1.25, in classes of 65 536; the first
     frame of a shape gets the smallest class); the mapper clamps to the capacity and raises a flag, in which case the
     frame is re-run once with room for the K it counted.
@@ -20,7 +20,6 @@ This is SURVEY.md 8(f)-1: in the reference that glue is ~24 % of the forward+bac
 from __future__ import annotations
 
 import ctypes
-from collections import namedtuple
 
 import torch
 
@@ -29,8 +28,8 @@ from .data_types import RasterConfig
 from .spherical_harmonics import check_sh_degree
 
 _K_HINT = {}  # (n, w, h, tile_size, use_depth16) -> (max overlaps, max tile population) seen for that shape
-# the backward of an unsharded frame: true = one gs_frame_bwd call, False = stage by stage, as a sharded frame's
-# (tests/conftest.py frame_path runs the fused-frame tests both ways)
+# the backward of an unsharded frame: true = one gs_frame_bwd call, False = the three calls a sharded frame makes
+# around its exchange (tests/conftest.py frame_path runs the fused-frame tests both ways)
 FRAME_CALLS = True
 _PINNED = {}  # device index -> ring of pinned int32[8] host buffers for the asynchronous count read-back
 
@@ -44,19 +43,9 @@ def _pinned_counts(dev: torch.device) -> torch.Tensor:
     return ring["bufs"][ring["at"]]
 
 
-def _off(t: torch.Tensor, floats: int) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr() + 4 * floats)
-
-
 _EVENTS = {}   # device index -> ring of (torch.cuda.Event, raw handle)
 _EMPTY = {}    # (device, shape) -> cached empty placeholder outputs
 _FRAMES = {}   # frame key -> (GsFrame, GsFrameLayout)
-
-
-# what the stage-by-stage backward reads of its forward, by name: views of the frame call's workspace (points (n, 7),
-# feats (n, F), image (h, w, F), img_depth None without render_depth, counts int32[8])
-_Frame = namedtuple("_Frame", "points feats slot_of indexes cam_pos tile_ranges o2p image alpha img_depth tile_order "
-                              "counts")
 
 
 class _Overflow(Exception):
@@ -172,7 +161,7 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
     dev = position.device
     n, w, full_h, C, config, shard = m["n"], m["w"], m["full_h"], m["C"], m["config"], m["shard"]
     render_depth = m["render_depth"]
-    # a sharded frame's backward runs stage by stage (the exchange sits in its middle) and clears its own rows
+    # a sharded frame's backward is split at its exchange, and the split calls clear their own rows
     prepare_backward = needs_grad and shard is None and bool(FRAME_CALLS)
     frame, L = _frame_for(n, C, m["degree"], w, full_h, depth_range, render_depth, use_depth16, render_median,
                           prepare_backward, k_cap, tile_hint, shard, config, world, rank)
@@ -195,7 +184,7 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
     num_tiles = max(L.tiles_x * L.tiles_y, 0)
     M = int(host[5]) if num_tiles > 0 else 0
     # rows_clean: gs_frame_fwd has zero-filled the gradient rows gs_frame_bwd accumulates into
-    m.update(V=V, K=K, h=h, F=F, col0=F - C, num_tiles=num_tiles, touched_count=M, frame=(frame, L),
+    m.update(V=V, K=K, F=F, col0=F - C, num_tiles=num_tiles, touched_count=M, frame=(frame, L),
              rows_clean=prepare_backward)
     f32, i32, i64 = ws.view(torch.float32), ws.view(torch.int32), ws.view(torch.int64)
     image = _carve(f32, L.image, (h, w, F))
@@ -210,19 +199,6 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
         # the frame call has already compacted the list (ascending rows) and cut it by owner; owned_rows = counts[2:4]
         lists = (_carve(i32, L.touched, (M,)), _carve(i64, L.owner_counts, (world,)), _carve(i32, L.counts + 8, (2,)))
     return outs, ws, lists
-
-
-def _record(m, ws):
-    """the _Frame the stage-by-stage backward reads: views of the frame call's workspace"""
-    frame, L = m["frame"]
-    n, w, h, F, num_tiles = m["n"], m["w"], m["h"], m["F"], m["num_tiles"]
-    f32, i32, i64 = ws.view(torch.float32), ws.view(torch.int32), ws.view(torch.int64)
-    return _Frame(_carve(f32, L.points, (n, 7)), _carve(f32, L.features, (n, F)), _carve(i32, L.slot_of, (n,)),
-                  _carve(i64, L.indexes, (n,)), _carve(f32, L.camera_pos, (3,)),
-                  _carve(i32, L.tile_ranges, (num_tiles, 2)), _carve(i32, L.overlap_to_point, (frame.k_capacity,)),
-                  _carve(f32, L.image, (h, w, F)), _carve(f32, L.alpha, (h, w)),
-                  _carve(f32, L.img_depth, (h, w)) if m["render_depth"] else None,
-                  _carve(i32, L.tile_order, (num_tiles,)), _carve(i32, L.counts, (8,)))
 
 
 def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, image_size,
@@ -293,164 +269,66 @@ def _add_centre_grad(d_T, d_centre, T):
         return d_T + (-(Y.T @ dY @ Y.T)).to(device=d_T.device, dtype=torch.float32)
 
 
-def _backward_stages(ctx, inputs, rec, g_image, g_points, g_depth, g_img_depth, g_img_var):
-    """the frame's backward, one C-ABI entry point per stage; returns the seven input gradients"""
-    position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
-    m = ctx.meta
-    lib = nv.lib()
-    dev = position.device
-    n, V, K, w, h, F, C, col0 = m["n"], m["V"], m["K"], m["w"], m["h"], m["F"], m["C"], m["col0"]
-    config = m["config"]
-    cfg = nv.make_config(config)
-    sh = nv.make_shard(m["shard"])
-    s = nv.stream()
-    RS = lib.gs_grad_row_floats(F)
-    rows = torch.zeros((max(V, 1), RS), dtype=torch.float32, device=dev)
-    if m["render_depth"] and V > 0 and h > 0 and any(g is not None for g in (g_image, g_img_depth, g_img_var)):
-        # assemble the gradient of the rasterized (H,W,2+C) image from the three upstream gradients
-        gf_ = g_image.contiguous() if g_image is not None else None
-        gd_ = g_img_depth.contiguous() if g_img_depth is not None else None
-        gv_ = g_img_var.contiguous() if g_img_var is not None else None
-        nv.require_device(gf_, gd_, gv_, what="render_gaussians backward")
-        g_image = torch.empty((h, w, F), dtype=torch.float32, device=dev)
-        nv.check(lib.gs_depth_split_bwd(h * w, C, nv.ptr(rec.img_depth), nv.ptr(rec.alpha), 1e-6, nv.ptr(gf_),
-                                        nv.ptr(gd_), nv.ptr(gv_), nv.ptr(g_image), s), "gs_depth_split_bwd")
-    if g_image is not None and V > 0 and h > 0 and K > 0:
-        gi = g_image.contiguous()
-        nv.require_device(gi, what="render_gaussians backward")
-        nv.check(lib.gs_raster_bwd(V, F, nv.ptr(rec.points), nv.ptr(rec.feats), nv.ptr(rec.tile_ranges),
-                                   nv.ptr(rec.o2p), K, w, m["full_h"], cfg, nv.ptr(rec.tile_order),
-                                   _off(rec.counts, 7), nv.ptr(rec.image), nv.ptr(gi), nv.ptr(rows), sh, s),
-                 "gs_raster_bwd")
-    if config.compute_point_heuristic and V > 0:
-        ctx.heur.copy_(rows[:V, 7 + F:9 + F])
-
-    def add_attached(pts_rows):
-        # gradients a caller attached to the projected splats / depths themselves (e.g. a regulariser): every
-        # rank of a sharded frame holds the same, complete one, so it is added AFTER the partial sums are reduced
-        if g_points is not None and V > 0:
-            pts_rows[:V, :7] += g_points
-        if g_depth is not None and V > 0 and m["render_depth"]:
-            pts_rows[:V, 7] += g_depth.reshape(-1)
-
-    extra_depth = None
-    if g_depth is not None and V > 0 and not m["render_depth"]:
-        extra_depth = g_depth.contiguous()
-
-    g_feat, g_feat_stride = _off(rows, 7 + col0), RS     # dL/d(SH colour) columns
-    g_pts, g_pts_stride = rows, RS                        # dL/d(points) [+ depth feature] columns
-    wait_points = None
-    if m["shard"] is not None:
-        # the exchanged partial gradients: colour columns, splat [+ depth feature] columns
-        rows_n = rows.shape[0]
-        pf = torch.empty((rows_n, C), dtype=torch.float32, device=dev)
-        pp = torch.empty((rows_n, 7 + col0), dtype=torch.float32, device=dev)
-        g_feat, g_feat_stride = nv.ptr(pf), C
-        g_pts, g_pts_stride = pp, 7 + col0
-    if m["shard"] is not None and m.get("sizes") is not None:
-        # Sparse exchange (parallel.py): one entry [row, 7 + F gradient words] per splat that can reach this rank's
-        # rows -- the mapper's own list -- instead of the dense rows, 7/8 of which are zeros on every rank of 8.
-        from . import parallel
-        touched, M = m["touched"], int(m["touched"].shape[0])
-        width = parallel.ENTRY_HEAD + F
-        entries = torch.empty((max(M, 1), width), dtype=torch.float32, device=dev)
-        nv.check(lib.gs_shard_pack_sparse(M, nv.ptr(touched), F, col0, nv.ptr(rows),
-                                          nv.ptr(rec.feats) if m["degree"] >= 0 else None, nv.ptr(entries), s),
-                 "gs_shard_pack_sparse")
-        table = m["sizes"].result()
-        group, rank = m["group"], m["rank"]
-        if m["grad_mode"] == "sharded":   # table[q][r] = entries rank q holds for owner r
-            lists = parallel.exchange_entries_sharded(entries, [int(x) for x in table[rank]],
-                                                      [int(table[q][rank]) for q in range(len(table))], group)
-        else:                             # table[q][0] = list length of rank q
-            lists = parallel.exchange_entries_replicated(entries, M, [int(t[0]) for t in table], group)
-        # every list in one pass over the dense rows (rank order inside each tile: the same sums on every rank;
-        # every row is written, so no clearing)
-        nl = len(lists)
-        ptrs = (ctypes.c_void_p * nl)(*[ent.data_ptr() if cnt else None for ent, cnt in lists])
-        cnts = (ctypes.c_int64 * nl)(*[cnt for _, cnt in lists])
-        tmp_bytes = 4 * nl * (-(-rows_n // 256) + 1)
-        tmp = torch.empty((tmp_bytes,), dtype=torch.uint8, device=dev)
-        nv.check(lib.gs_shard_merge_sparse(nl, ptrs, cnts, F, col0, rows_n, nv.ptr(pf), nv.ptr(pp),
-                                           nv.ptr(m.get("owned_rows")), nv.ptr(tmp), tmp_bytes, s),
-                 "gs_shard_merge_sparse")
-    elif m["shard"] is not None:
-        # Every rank rendered different rows: the per-Gaussian partial gradients are summed over the
-        # ranks, 4*(7+F) bytes per visible Gaussian in all.  Two collectives, colour columns first: the SH
-        # adjoint only needs those and runs while the splat columns are still in flight.
-        from .parallel import _reduce_partial_gradients
-        # (packed by one kernel, which also applies the SH clamp mask: only the ranks that rasterized a splat know it)
-        nv.check(lib.gs_shard_pack_grads(rows_n, F, col0, nv.ptr(rows), nv.ptr(rec.feats) if m["degree"] >= 0 else None,
-                                         nv.ptr(pf), nv.ptr(pp), s), "gs_shard_pack_grads")
-        wait_points = _reduce_partial_gradients(pf, pp, m["group"])
-    else:
-        _publish(ctx, rows, V)
-        add_attached(rows)
-
-    # grad_mode "sharded": the adjoints run on this rank's index range [lo, hi) only -- the same kernels on base
-    # pointers moved to row `lo` (every array they touch is indexed by the Gaussian, the gradient rows through
-    # slot_of) -- and the gradients come out range-shaped
-    lo, hi = m["owned_range"] if m["owned_range"] is not None else (0, n)
-    nr = hi - lo
-    need_T, need_proj = ctx.camera_grads
-
-    def at(t, row):  # pointer to row `row` of a per-Gaussian tensor
-        return ctypes.c_void_p(t.data_ptr() + row * t.stride(0) * t.element_size())
-
-    d_feature = torch.empty((nr, *feature.shape[1:]), dtype=torch.float32, device=dev)
-    # camera matrix under optimisation: the SH view direction depends on the camera centre = inverse(T)[:3, 3]
-    # (reference perspective/params.py:76-78), so the SH adjoint also returns dL/d(centre) and the 4x4 inverse is
-    # differentiated below (pose refinement is rare: a handful of tiny torch ops, off the common path)
-    d_centre = None
-    if m["degree"] >= 1 and need_T:
-        d_centre = torch.zeros((3,), dtype=torch.float32, device=dev)
-    if m["degree"] >= 0:
-        nv.check(lib.gs_sh_bwd(nr, V, C, m["degree"], at(feature, lo), at(position, lo), nv.ptr(rec.indexes), 1,
-                               at(rec.slot_of, lo), nv.ptr(rec.cam_pos), g_feat, g_feat_stride, _off(rec.feats, col0),
-                               F, nv.ptr(d_feature), None, nv.ptr(d_centre), s), "gs_sh_bwd")
-    else:
-        nv.check(lib.gs_feature_gather_bwd(nr, C, at(rec.slot_of, lo), g_feat, g_feat_stride, nv.ptr(d_feature), s),
-                 "gs_feature_gather_bwd")
-    if wait_points is not None:
-        wait_points.wait()
-    if m["shard"] is not None:
-        _publish(ctx, g_pts, V)
-        add_attached(g_pts)
-
-    f32r = dict(dtype=torch.float32, device=dev)
-    d_pos, d_ls = torch.empty((nr, 3), **f32r), torch.empty((nr, 3), **f32r)
-    d_rot, d_al = torch.empty((nr, 4), **f32r), torch.empty((nr, 1), **f32r)
-    d_T = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_T else None
-    d_proj = torch.empty((4,), dtype=torch.float32, device=dev) if need_proj else None
-    nbytes = lib.gs_project_bwd_scratch_bytes(nr) if (need_T or need_proj) else 0
-    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
-    if m["render_depth"]:
-        gd, gd2, gstride = _off(g_pts, 7), _off(g_pts, 8), g_pts_stride
-    else:
-        gd, gd2, gstride = nv.ptr(extra_depth), None, 1
-    nv.check(lib.gs_project_bwd(nr, V, at(position, lo), at(log_scaling, lo), at(rotation, lo), at(alpha_logit, lo),
-                                nv.ptr(T), nv.ptr(proj), w, m["full_h"], cfg, at(rec.slot_of, lo), nv.ptr(g_pts),
-                                g_pts_stride, gd, gd2, gstride, nv.ptr(d_pos), nv.ptr(d_ls), nv.ptr(d_rot),
-                                nv.ptr(d_al), nv.ptr(d_T), nv.ptr(d_proj), nv.ptr(scratch), nbytes, s),
-             "gs_project_bwd")
-    return (d_pos, d_ls, d_rot, d_al, d_feature, _add_centre_grad(d_T, d_centre, T), d_proj)
+def _exchange(m, rows, feats):
+    """a sharded frame's partial gradients, summed over the ranks: (colour columns (V', C), splat [+ depth feature]
+    columns (V', 7 + col0), the handle of a collective still in flight or None), V' = max(V, 1); `feats`: the frame's
+    feature rows, whose SH clamp mask the packs apply (only the ranks that rasterized a splat know it)"""
+    from . import parallel
+    lib, dev, s = nv.lib(), rows.device, nv.stream()
+    F, C, col0 = m["F"], m["C"], m["col0"]
+    rows_n = rows.shape[0]
+    pf = torch.empty((rows_n, C), dtype=torch.float32, device=dev)
+    pp = torch.empty((rows_n, 7 + col0), dtype=torch.float32, device=dev)
+    if m.get("sizes") is None:
+        # Every rank rendered different rows: the per-Gaussian partial gradients are summed over the ranks, 4*(7+F)
+        # bytes per visible Gaussian in all.  Two collectives, colour columns first: the SH adjoint only needs those and
+        # runs while the splat columns are still in flight.
+        nv.check(lib.gs_shard_pack_grads(rows_n, F, col0, nv.ptr(rows), feats, nv.ptr(pf), nv.ptr(pp), s),
+                 "gs_shard_pack_grads")
+        return pf, pp, parallel._reduce_partial_gradients(pf, pp, m["group"])
+    # Sparse exchange (parallel.py): one entry [row, 7 + F gradient words] per splat that can reach this rank's rows --
+    # the mapper's own list -- instead of the dense rows, 7/8 of which are zeros on every rank of 8.
+    touched, M = m["touched"], int(m["touched"].shape[0])
+    entries = torch.empty((max(M, 1), parallel.ENTRY_HEAD + F), dtype=torch.float32, device=dev)
+    nv.check(lib.gs_shard_pack_sparse(M, nv.ptr(touched), F, col0, nv.ptr(rows), feats, nv.ptr(entries), s),
+             "gs_shard_pack_sparse")
+    table = m["sizes"].result()
+    group, rank = m["group"], m["rank"]
+    if m["grad_mode"] == "sharded":   # table[q][r] = entries rank q holds for owner r
+        lists = parallel.exchange_entries_sharded(entries, [int(x) for x in table[rank]],
+                                                  [int(table[q][rank]) for q in range(len(table))], group)
+    else:                             # table[q][0] = list length of rank q
+        lists = parallel.exchange_entries_replicated(entries, M, [int(t[0]) for t in table], group)
+    # every list in one pass over the dense rows (rank order inside each tile: the same sums on every rank; every row is
+    # written, so no clearing)
+    nl = len(lists)
+    ptrs = (ctypes.c_void_p * nl)(*[ent.data_ptr() if cnt else None for ent, cnt in lists])
+    cnts = (ctypes.c_int64 * nl)(*[cnt for _, cnt in lists])
+    tmp_bytes = 4 * nl * (-(-rows_n // 256) + 1)
+    tmp = torch.empty((tmp_bytes,), dtype=torch.uint8, device=dev)
+    nv.check(lib.gs_shard_merge_sparse(nl, ptrs, cnts, F, col0, rows_n, nv.ptr(pf), nv.ptr(pp),
+                                       nv.ptr(m.get("owned_rows")), nv.ptr(tmp), tmp_bytes, s), "gs_shard_merge_sparse")
+    return pf, pp, None
 
 
-def _backward_call(ctx, inputs, ws, g_image, g_points, g_depth, g_img_depth, g_img_var):
-    """the frame's backward as one gs_frame_bwd call on the workspace of its gs_frame_fwd"""
+def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
+    """the frame's backward on the workspace of its gs_frame_fwd: one gs_frame_bwd call when the forward prepared it,
+    otherwise three -- rasterizer, colour adjoint, projection adjoint -- with a sharded frame's exchange of its partial
+    gradients after the first; returns the seven input gradients"""
+    saved = ctx.saved_tensors
+    inputs, ws = saved[:7], saved[7]
     position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
     m = ctx.meta
     frame, L = m["frame"]
     lib = nv.lib()
     dev = position.device
-    V, K, F = m["V"], m["K"], m["F"]
+    n, V, K, F = m["n"], m["V"], m["K"], m["F"]
     RS = L.grad_row_floats
-    f32 = ws.view(torch.float32)
     scratch = torch.empty((L.bwd_scratch_bytes,), dtype=torch.uint8, device=dev)
-    rows_off = L.grad_rows if L.grad_rows >= 0 else None
-    rows = (f32.as_strided((max(V, 1), RS), (RS, 1), L.grad_rows // 4) if rows_off is not None
-            else scratch.view(torch.float32).as_strided((max(V, 1), RS), (RS, 1), L.b_grad_rows // 4))
-    if rows_off is not None and not m["rows_clean"]:
+    whole = bool(frame.prepare_backward)  # the forward has zero-filled gradient rows in the workspace
+    base, off = (ws, L.grad_rows) if whole else (scratch, L.b_grad_rows)
+    rows = base.view(torch.float32).as_strided((max(V, 1), RS), (RS, 1), off // 4)
+    if whole and not m["rows_clean"]:
         rows.zero_()  # a second backward through the same frame (retain_graph): the rows hold the first one's sums
     m["rows_clean"] = False
     gi = gd_ = gv_ = None
@@ -463,29 +341,51 @@ def _backward_call(ctx, inputs, ws, g_image, g_points, g_depth, g_img_depth, g_i
     att_d = g_depth.contiguous() if (g_depth is not None and V > 0) else None
     nv.require_device(gi, gd_, gv_, att_p, att_d, what="render_gaussians backward")
     need_T, need_proj = ctx.camera_grads
-    # one allocation for the five parameter gradients
-    sizes = (position.numel(), log_scaling.numel(), rotation.numel(), alpha_logit.numel(), feature.numel())
+    # grad_mode "sharded": the adjoints run on this rank's index range [lo, hi) only and the gradients come out
+    # range-shaped; one allocation for the five parameter gradients
+    lo, hi = m["owned_range"] if m["owned_range"] is not None else (0, n)
+    nr = hi - lo
+    params = (position, log_scaling, rotation, alpha_logit, feature)
+    sizes = [t.numel() if nr == n else t.numel() // n * nr for t in params]
     flat = torch.empty((sum(sizes),), dtype=torch.float32, device=dev)
     outs, at = [], 0
-    for t, sz in zip((position, log_scaling, rotation, alpha_logit, feature), sizes):
-        outs.append(flat.as_strided(t.shape, t.stride(), at))
+    for t, sz in zip(params, sizes):
+        outs.append(flat.as_strided(t.shape if nr == n else (nr, *t.shape[1:]), t.stride(), at))
         at += sz
-    d_pos, d_ls, d_rot, d_al, d_feature = outs
     d_T = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_T else None
     d_proj = torch.empty((4,), dtype=torch.float32, device=dev) if need_proj else None
     d_centre = None
     if m["degree"] >= 1 and need_T:
         d_centre = torch.zeros((3,), dtype=torch.float32, device=dev)
-    nv.check(lib.gs_frame_bwd(ctypes.byref(frame), nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation),
-                              nv.ptr(alpha_logit), nv.ptr(feature), nv.ptr(T), nv.ptr(proj), nv.ptr(ws),
-                              L.workspace_bytes, nv.ptr(scratch), L.bwd_scratch_bytes, V, K, nv.ptr(gi),
-                              nv.ptr(gd_), nv.ptr(gv_), nv.ptr(att_p), nv.ptr(att_d), nv.ptr(d_pos), nv.ptr(d_ls),
-                              nv.ptr(d_rot), nv.ptr(d_al), nv.ptr(d_feature), nv.ptr(d_T), nv.ptr(d_proj),
-                              nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES), nv.stream()), "gs_frame_bwd")
+
+    def call(stages=None, colours=None, splats=None):
+        # stages None: the whole backward; colours / splats: the summed partial gradients of a sharded frame
+        part = None if stages is None else ctypes.byref(nv.GsFrameBwdPart(
+            stages.start, stages.stop, None if colours is None else colours.data_ptr(),
+            None if splats is None else splats.data_ptr(), 0 if colours is None else colours.stride(0),
+            0 if splats is None else splats.stride(0), lo, hi))
+        nv.check(lib.gs_frame_bwd_part(ctypes.byref(frame), *map(nv.ptr, inputs), nv.ptr(ws), L.workspace_bytes,
+                                       nv.ptr(scratch), L.bwd_scratch_bytes, V, K, nv.ptr(gi), nv.ptr(gd_), nv.ptr(gv_),
+                                       nv.ptr(att_p), nv.ptr(att_d), *map(nv.ptr, outs), nv.ptr(d_T), nv.ptr(d_proj),
+                                       nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), nv.stream(),
+                                       part), "gs_frame_bwd_part")
+
+    call(None if whole else range(nv.GS_BWD_RASTER, nv.GS_BWD_COLOURS))
     if m["config"].compute_point_heuristic and V > 0:
         ctx.heur.copy_(rows[:V, 7 + F:9 + F])
-    _publish(ctx, rows, V, att_p)  # the rows hold the attached gradient as well
-    return (d_pos, d_ls, d_rot, d_al, d_feature, _add_centre_grad(d_T, d_centre, T), d_proj)
+    if whole:
+        _publish(ctx, rows, V, att_p)  # the rows hold the attached gradient as well
+    else:
+        pf = pp = wait = None
+        if m["shard"] is not None:
+            feats = ctypes.c_void_p(ws.data_ptr() + L.features) if m["degree"] >= 0 else None
+            pf, pp, wait = _exchange(m, rows, feats)
+        call(range(nv.GS_BWD_COLOURS, nv.GS_BWD_PROJECT), colours=pf)
+        if wait is not None:
+            wait.wait()
+        _publish(ctx, rows if pp is None else pp, V)  # before the PROJECT call adds the attached gradient
+        call(range(nv.GS_BWD_PROJECT, nv.GS_BWD_STAGES), splats=pp)
+    return (*outs, _add_centre_grad(d_T, d_centre, T), d_proj)
 
 
 class _FrameRender(torch.autograd.Function):
@@ -500,14 +400,7 @@ class _FrameRender(torch.autograd.Function):
     @nv.on_tensor_device
     def backward(ctx, g_image, _g_alpha, g_points, g_depth, _g_idx, _g_vis, _g_heur, g_img_depth, g_img_var,
                  _g_median=None):
-        # gs_frame_bwd for a frame whose gs_frame_fwd prepared it, else stage by stage on views of the workspace
-        saved = ctx.saved_tensors
-        inputs, ws = saved[:7], saved[7]
-        if ctx.meta["frame"][0].prepare_backward:
-            d = _backward_call(ctx, inputs, ws, g_image, g_points, g_depth, g_img_depth, g_img_var)
-        else:
-            d = _backward_stages(ctx, inputs, _record(ctx.meta, ws), g_image, g_points, g_depth, g_img_depth,
-                                 g_img_var)
+        d = _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var)
         return d + (None,) * (len(ctx.needs_input_grad) - len(d))
 
 

@@ -163,6 +163,25 @@ def test_frame_layout_is_computed_on_the_host():
     rc = lib.gs_frame_bwd(ctypes.byref(sh), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None, None)
     assert rc == -2 and b"sharded" in lib.gs_last_error()
 
+    # gs_frame_bwd_part: a stage range and a row range, checked before the buffers; a NULL part is gs_frame_bwd
+    rc = lib.gs_frame_bwd_part(ctypes.byref(sh), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None, None, None)
+    assert rc == -2 and b"sharded" in lib.gs_last_error()
+    assert ctypes.sizeof(_native.GsFrameBwdPart) == 48
+
+    def bwd(fr, first, end, rows=(0, 1000)):
+        part = _native.GsFrameBwdPart(first_stage=first, end_stage=end, row_begin=rows[0], row_end=rows[1])
+        return lib.gs_frame_bwd_part(ctypes.byref(fr), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None,
+                                     None, ctypes.byref(part))
+    R, C, P, END = _native.GS_BWD_RASTER, _native.GS_BWD_COLOURS, _native.GS_BWD_PROJECT, _native.GS_BWD_STAGES
+    assert bwd(sh, R, C + 1) == -2 and b"sharded" in lib.gs_last_error()   # the exchange sits between the two
+    assert bwd(sh, R, END) == -2
+    for first, end in ((R, R), (P, C), (-1, C), (C, END + 1)):
+        assert bwd(f, first, end) == -1 and b"stages" in lib.gs_last_error(), (first, end)
+    for rows in ((-1, 10), (10, 9), (0, 1001)):
+        assert bwd(f, R, END, rows) == -1 and b"rows" in lib.gs_last_error(), rows
+    # well-formed parts get as far as the buffer checks
+    assert bwd(sh, R, C) == -4 and bwd(sh, C, END, (200, 400)) == -4 and bwd(f, R, END, (1000, 1000)) == -4
+
 
 def test_sparse_exchange_entry_points_validate_on_the_host():
     """the sparse exchange's entry points (round 3) refuse bad arguments before any launch; empty calls are no-ops"""

@@ -19,7 +19,7 @@ for round_ in range(3):  # the two backward paths alternating, so that clock / b
         torch.cuda.synchronize(); t0 = time.perf_counter(); c0 = time.process_time()
         for _ in range(300): step()
         c1 = time.process_time(); torch.cuda.synchronize()
-        print(f"round {round_}: ms/step (gs_frame_fwd, then {'gs_frame_bwd' if calls else 'the backward stage by stage'}):",
+        print(f"round {round_}: ms/step (gs_frame_fwd, then {'one gs_frame_bwd call' if calls else 'three gs_frame_bwd calls'}):",
               round((time.perf_counter() - t0) / 300 * 1e3, 4), " process CPU ms/step:", round((c1 - c0) / 300 * 1e3, 4))
 fused.FRAME_CALLS = True
 # forward and backward apart (each followed by a device synchronisation)
