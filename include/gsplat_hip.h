@@ -35,6 +35,7 @@ typedef enum GsStatus {
 } GsStatus;
 
 #define GS_MAX_FEATURES 32
+#define GS_MAX_WIDE_FEATURES 512 /* gs_raster_fwd_wide / gs_raster_bwd_wide */
 #define GS_MAX_SH_CHANNELS 8
 
 /* Mirrors RasterConfig (data_types.py:13-39) field for field. */
@@ -322,6 +323,21 @@ int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const fl
                   void* stream);
 int gs_raster_bwd_unpack(int64_t v, int32_t num_features, const float* grad_rows, float* grad_points,
                          float* grad_features, float* point_heuristic, void* stream);
+
+/* Wide features: the forward and backward above for 1 <= num_features <= GS_MAX_WIDE_FEATURES (features lifted from
+ * 2D models), honouring every GsRasterConfig field gs_raster_fwd / gs_raster_bwd honour.  No tile order, heavy-tile
+ * split or row shard.  The forward writes image (H,W,F) and alpha (H,W), and adds into visibility (V) as gs_raster_fwd.
+ * The backward adds into the caller's zero-filled grad_points (V,7), grad_features (V,F) and, when
+ * cfg->compute_point_heuristic, point_heuristic (V,2); it refuses use_alpha_blending = 0 as gs_raster_bwd does.
+ */
+int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
+                       const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                       int32_t height, const GsRasterConfig* cfg, float* image, float* alpha, float* visibility,
+                       void* stream);
+int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
+                       const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                       int32_t height, const GsRasterConfig* cfg, const float* image, const float* grad_image,
+                       float* grad_points, float* grad_features, float* point_heuristic, void* stream);
 
 /* ------------------------------------------------- plain features (render_gaussians(use_sh=False)) --
  * replaces: `features = gaussians.feature[indexes]` (renderer.py:166) and its index backward, inside the fused frame:

@@ -23,6 +23,7 @@
 // Roofline: algorithmic HBM bytes 8T + K(4+28+4F) + 8PF + 4(7+F)K; VALU-bound.
 
 #include "gs_common.h"
+#include "raster_pdf.h"
 
 namespace {
 
@@ -55,34 +56,6 @@ __device__ __forceinline__ void tile_origin(const BwdArgs& a, int tile, int& x0,
   x0 = (tile - lty * a.tiles_wide) * a.tile_size;
   y0 = gs_shard_global_row(a.sh, lty) * a.tile_size;
   yout0 = lty * a.tile_size;
-}
-
-__device__ __forceinline__ void s_sig_grad(float x, float inv_sigma, float& s, float& ds_dx, float& ds_dsig) {
-  // taichi_lib/generic.py:360-369
-  const float z = x * inv_sigma;
-  s = gs_rcp_fast(1.0f + gs_exp2_fast((-1.6f * z - 0.07f * z * z * z) * 1.44269504088896341f));
-  const float d = (1.6f + 0.21f * z * z) * s * (1.0f - s);
-  ds_dx = d * inv_sigma;
-  ds_dsig = ds_dx * -z;
-}
-
-// The antialiased pdf's sigmoid S(z) = 1 / (1 + exp(-(1.6 z + 0.07 z^3))) (taichi_lib/generic.py:341-369) and its
-// derivative in 15 issue slots: a = S(z), d = dS/dz = (1.6 + 0.21 z^2) S (1 - S); the log2(e) factors are folded into
-// the polynomial.  (S (1 - S) as a (1 - a), not e a^2: far out in the tail e overflows to inf while a is an exact 0.)
-__device__ __forceinline__ void s_sig_parts(float z, float& a, float& d) {
-  const float z2 = z * z;
-  const float e = gs_exp2_fast(z * __builtin_fmaf(-0.07f * 1.44269504088896341f, z2, -1.6f * 1.44269504088896341f));
-  a = gs_rcp_fast(1.0f + e);
-  d = __builtin_fmaf(0.21f, z2, 1.6f) * (a * (1.0f - a));
-}
-// ... in two halves: the value alone decides whether a pixel takes anything from the splat; the derivative is only
-// formed for the pixels that do (GS_BWD_HIT_EXEC: under their EXEC mask, skipped when the sub-block has none)
-__device__ __forceinline__ float s_sig_value(float z) {
-  const float e = gs_exp2_fast(z * __builtin_fmaf(-0.07f * 1.44269504088896341f, z * z, -1.6f * 1.44269504088896341f));
-  return gs_rcp_fast(1.0f + e);
-}
-__device__ __forceinline__ float s_sig_slope(float z, float a) {
-  return __builtin_fmaf(0.21f, z * z, 1.6f) * (a * (1.0f - a));
 }
 
 #ifndef GS_BWD_WAVES

@@ -23,6 +23,7 @@
 // VALU-bound (about 20 VALU + 1 v_exp_f32 per evaluated pixel-splat pair).
 
 #include "gs_common.h"
+#include "raster_pdf.h"
 
 namespace {
 
@@ -55,25 +56,6 @@ __device__ __forceinline__ void tile_origin(const FwdArgs& a, int tile, int& x0,
   x0 = (tile - lty * a.tiles_wide) * a.tile_size;
   y0 = gs_shard_global_row(a.sh, lty) * a.tile_size;
   yout0 = lty * a.tile_size;
-}
-
-__device__ __forceinline__ float s_sig(float x, float inv_sigma) {
-  const float z = x * inv_sigma;
-  const float e = -1.6f * z - 0.07f * z * z * z;
-  return gs_rcp_fast(1.0f + gs_exp2_fast(e * 1.44269504088896341f));
-}
-
-// One axis of the antialiased pdf (taichi_lib/generic.py:341-357): D(t) = S((t + 0.5) / s) - S((t - 0.5) / s) with
-// S(z) = 1 / (1 + e(z)), e(z) = exp(-(1.6 z + 0.07 z^3)), returned as num / den = (e_b - e_a) / ((1 + e_a)(1 + e_b)) so
-// that both axes share ONE reciprocal.  D is even (S(-z) = 1 - S(z)), so |t| is used: a >= 0 keeps e_a <= 1, and b is
-// clamped at -5, where S(b) < 5e-8 (e_b stays below 2e7: no overflow in the product of the two axes).
-__device__ __forceinline__ void aa_axis(float t, float inv_sigma, float& num, float& den) {
-  const float u = fabsf(t);
-  const float za = (u + 0.5f) * inv_sigma, zb = fmaxf((u - 0.5f) * inv_sigma, -5.0f);
-  const float c1 = -1.6f * 1.44269504088896341f, c3 = -0.07f * 1.44269504088896341f;
-  const float ea = gs_exp2_fast(za * (c1 + c3 * za * za)), eb = gs_exp2_fast(zb * (c1 + c3 * zb * zb));
-  num = eb - ea;
-  den = (1.0f + ea) * (1.0f + eb);
 }
 
 // NB: 8x8 sub-blocks per wave (1, 2 or 4; gs_raster_sub_blocks picks it from the grid size).  FP: padded feature width.

@@ -2,7 +2,8 @@
 
 Operator interface of the reference rasterizer/function.py:96-161: `rasterize_with_tiles`,
 `rasterize`, `RasterOut`.  image / image_weight are (H,W,F) / (H,W); image_weight, visibility and
-point_heuristic are non-differentiable (:72); gradients flow to gaussians2d and features.
+point_heuristic are non-differentiable (:72); gradients flow to gaussians2d and features.  Up to 32 feature channels
+run the narrow kernels, 33 to 512 the wide ones (csrc/raster_wide.hip).
 """
 from __future__ import annotations
 
@@ -14,6 +15,10 @@ import torch
 from .. import _native as nv
 from ..data_types import RasterConfig
 from ..mapper.tile_mapper import map_to_tiles
+
+# widest features of gs_raster_fwd / gs_raster_bwd (include/gsplat_hip.h GS_MAX_FEATURES); wider ones, up to
+# GS_MAX_WIDE_FEATURES = 512, take gs_raster_fwd_wide / gs_raster_bwd_wide
+MAX_FEATURES = 32
 
 RasterOut = NamedTuple('RasterOut', [
     ('image', torch.Tensor),
@@ -43,9 +48,14 @@ class _RasterFunction(torch.autograd.Function):
         want_vis = config.compute_visibility or config.compute_point_heuristic
         vis = (torch.zeros((v,), dtype=torch.float32, device=dev) if want_vis
                else torch.empty((0,), dtype=torch.float32, device=dev))
-        nv.check(lib.gs_raster_fwd(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
-                                   nv.make_config(config), None, None, nv.ptr(image), nv.ptr(alpha),
-                                   nv.ptr(vis) if want_vis else None, None, nv.stream()), "gs_raster_fwd")
+        if F <= MAX_FEATURES:
+            nv.check(lib.gs_raster_fwd(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                       nv.make_config(config), None, None, nv.ptr(image), nv.ptr(alpha),
+                                       nv.ptr(vis) if want_vis else None, None, nv.stream()), "gs_raster_fwd")
+        else:
+            nv.check(lib.gs_raster_fwd_wide(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w,
+                                            h, nv.make_config(config), nv.ptr(image), nv.ptr(alpha),
+                                            nv.ptr(vis) if want_vis else None, nv.stream()), "gs_raster_fwd_wide")
         if not config.compute_visibility:
             vis_out = torch.empty((0,), dtype=torch.float32, device=dev) if not want_vis else vis
         else:
@@ -66,6 +76,14 @@ class _RasterFunction(torch.autograd.Function):
         config = ctx.config
         gi = grad_image.contiguous()
         nv.require_device(gi, what="rasterize backward")
+        if F > MAX_FEATURES:
+            grad_g = torch.zeros_like(g)
+            grad_f = torch.zeros_like(f)
+            heur = ctx.heur if config.compute_point_heuristic else None
+            nv.check(lib.gs_raster_bwd_wide(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w,
+                                            h, nv.make_config(config), nv.ptr(image), nv.ptr(gi), nv.ptr(grad_g),
+                                            nv.ptr(grad_f), nv.ptr(heur), nv.stream()), "gs_raster_bwd_wide")
+            return grad_g, grad_f, None, None, None, None
         row = lib.gs_grad_row_floats(F)
         rows = torch.zeros((v, row), dtype=torch.float32, device=g.device)
         nv.check(lib.gs_raster_bwd(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
