@@ -11,8 +11,8 @@
  *   - return value: 0 on success, negative GsStatus on failure; gs_last_error() returns a
  *     thread-local message for the last failure on the calling thread.
  *   - re-entrant, no global mutable state.
- *   - f32 only (the reference's f64 instantiations exist for gradcheck only,
- *     taichi_lib/__init__.py:8-14; f64 checks run against the CPU oracle in tests/).
+ *   - f32, except the gs_*_f64 entry points at the end: float64 projection, SH and rasterizer for
+ *     gradcheck (the reference's f64 instantiations, taichi_lib/__init__.py:8-14).
  *
  * "replaces" lines cite the reference interface each entry point stands in for (paths relative
  * to /root/reference/taichi_splatting/).  The reference-side binding is in INTEGRATION.md.
@@ -496,6 +496,71 @@ int gs_optim_step(int32_t laprop, int32_t vector_group, int64_t rows, int32_t di
                   const float* weight, float* m, float* v, const float* total_weight, const float* grad, float lr,
                   float beta1, float beta2, float eps, int32_t bias_correction, float* lr_step,
                   const float* row_scale, float* param, const float* mask_lr, const float* point_lr, void* stream);
+
+/* ------------------------------------------------------------------- float64 operators --
+ * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
+ * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  They restate the
+ * reference formulas literally with IEEE sqrt / exp / log; none of the f32 kernels' reformulations.  Every result is
+ * bit-reproducible: no float atomic feeds an output (per-entry records summed in a fixed order).  Scope: no tile
+ * order, heavy-tile split, row shard or stride options; features up to GS_MAX_FEATURES; forward_cut does not exist
+ * here (the forward blends a tile's whole list, as the reference does). */
+typedef struct GsRasterConfigF64 {
+  int32_t tile_size;  /* 8, 16 or 32 */
+  int32_t antialias;
+  int32_t use_alpha_blending;
+  int32_t compute_point_heuristic;
+  int32_t compute_visibility;
+  double clamp_margin;
+  double blur_cov;
+  double clamp_max_alpha;
+  double alpha_threshold;
+  double saturate_threshold;
+} GsRasterConfigF64;
+
+/* gs_project_fwd / gs_project_bwd in f64 (same tensors, same compaction: points (V,7), depth (V,1), ndc_depth (V,1),
+ * indexes (V) int64 ascending, slot_of (n), *num_visible).  Camera gradients (d_T_camera_world 4x4, d_projection 4;
+ * either may be NULL) are per-workgroup partials reduced in a fixed order.  grad_points / grad_depth may be NULL. */
+int64_t gs_project_f64_scratch_bytes(int64_t n);
+int gs_project_fwd_f64(int64_t n, const double* position, const double* log_scaling, const double* rotation,
+                       const double* alpha_logit, const double* T_camera_world, const double* projection,
+                       int32_t width, int32_t height, double near_plane, double far_plane,
+                       const GsRasterConfigF64* cfg, double* points, double* depth, double* ndc_depth,
+                       int64_t* indexes, int32_t* slot_of, int32_t* num_visible, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+int64_t gs_project_bwd_f64_scratch_bytes(int64_t n);
+int gs_project_bwd_f64(int64_t n, const double* position, const double* log_scaling, const double* rotation,
+                       const double* alpha_logit, const double* T_camera_world, const double* projection,
+                       int32_t width, int32_t height, const GsRasterConfigF64* cfg, const int32_t* slot_of,
+                       const double* grad_points, const double* grad_depth, double* d_position,
+                       double* d_log_scaling, double* d_rotation, double* d_alpha_logit, double* d_T_camera_world,
+                       double* d_projection, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* gs_sh_fwd / gs_sh_bwd in f64: params (n,C,D), positions (n,3), indexes (v) int64 in [0, n), repeats allowed,
+ * camera_pos 3 doubles; out (v,C).  The backward writes the dense d_params (n,C,D), d_positions (n,3) (may be NULL)
+ * and d_camera_pos (3, may be NULL); a Gaussian listed several times sums its entries in ascending list order. */
+int gs_sh_fwd_f64(int64_t v, int32_t channels, int32_t degree, const double* params, const double* positions,
+                  const int64_t* indexes, const double* camera_pos, double* out, void* stream);
+int64_t gs_sh_bwd_f64_scratch_bytes(int64_t n, int64_t v);
+int gs_sh_bwd_f64(int64_t n, int64_t v, int32_t channels, int32_t degree, const double* params,
+                  const double* positions, const int64_t* indexes, const double* camera_pos, const double* grad_out,
+                  double* d_params, double* d_positions, double* d_camera_pos, void* scratch, int64_t scratch_bytes,
+                  void* stream);
+
+/* gs_raster_fwd / gs_raster_bwd in f64 for 1 <= num_features <= GS_MAX_FEATURES.  The tile ranges must be disjoint (as
+ * the mapper makes them).  Forward: image (H,W,F), alpha (H,W), visibility (V, may be NULL unless
+ * cfg->compute_visibility; written, not added to).  Backward: grad_points (V,7), grad_features (V,F) and, when
+ * cfg->compute_point_heuristic, point_heuristic (V,2) are written (zero for splats in no list); use_alpha_blending = 0
+ * is refused as in gs_raster_bwd.  scratch: gs_raster_f64_scratch_bytes(v, k, num_features), for either call. */
+int64_t gs_raster_f64_scratch_bytes(int64_t v, int64_t k, int32_t num_features);
+int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
+                      const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                      int32_t height, const GsRasterConfigF64* cfg, double* image, double* alpha,
+                      double* visibility, void* scratch, int64_t scratch_bytes, void* stream);
+int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
+                      const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                      int32_t height, const GsRasterConfigF64* cfg, const double* image, const double* grad_image,
+                      double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
+                      int64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

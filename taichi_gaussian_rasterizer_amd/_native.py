@@ -2,7 +2,8 @@
 
 The HIP library is the ONLY compute backend of this package: there is no CPU fallback and no
 torch re-implementation behind these calls.  If the shared library is missing, or a tensor is not
-a float32 CUDA(HIP) tensor, the call raises -- it never silently routes elsewhere.
+a float32 CUDA(HIP) tensor (float64 where an operator has f64 kernels), the call raises -- it never
+silently routes elsewhere.
 """
 from __future__ import annotations
 
@@ -26,6 +27,14 @@ class GsRasterConfig(ctypes.Structure):
                 ("compute_visibility", c_int32), ("clamp_margin", c_float), ("blur_cov", c_float),
                 ("clamp_max_alpha", c_float), ("alpha_threshold", c_float), ("saturate_threshold", c_float),
                 ("forward_cut", c_float), ("tune_wave_sub_blocks", c_int32), ("tune_no_heavy_split", c_int32)]
+
+
+class GsRasterConfigF64(ctypes.Structure):
+    """include/gsplat_hip.h GsRasterConfigF64: the float64 entry points' config, thresholds at double precision."""
+    _fields_ = [("tile_size", c_int32), ("antialias", c_int32), ("use_alpha_blending", c_int32),
+                ("compute_point_heuristic", c_int32), ("compute_visibility", c_int32), ("clamp_margin", c_double),
+                ("blur_cov", c_double), ("clamp_max_alpha", c_double), ("alpha_threshold", c_double),
+                ("saturate_threshold", c_double)]
 
 
 class GsRowShard(ctypes.Structure):
@@ -70,6 +79,7 @@ TUNING = {"wave_sub_blocks": int(os.environ.get("GS_RASTER_NB", "0") or 0),
 
 
 _CFG = POINTER(GsRasterConfig)
+_CFG64 = POINTER(GsRasterConfigF64)
 _FRAME = POINTER(GsFrame)
 _SHARD = POINTER(GsRowShard)
 _P = c_void_p
@@ -133,6 +143,20 @@ SIGNATURES = {
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gs_frame_bwd_part": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(GsFrameBwdPart)]),
+    "gs_project_f64_scratch_bytes": (_I64, [_I64]),
+    "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
+                                           _P, _P, _P, _I64, _P]),
+    "gs_project_bwd_f64_scratch_bytes": (_I64, [_I64]),
+    "gs_project_bwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _CFG64, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _I64, _P]),
+    "gs_sh_fwd_f64": (ctypes.c_int, [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "gs_sh_bwd_f64_scratch_bytes": (_I64, [_I64, _I64]),
+    "gs_sh_bwd_f64": (ctypes.c_int, [_I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "gs_raster_f64_scratch_bytes": (_I64, [_I64, _I64, _I32]),
+    "gs_raster_fwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _I64,
+                                          _P]),
+    "gs_raster_bwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P, _P,
+                                          _I64, _P]),
 }
 
 _lib = None
@@ -264,6 +288,16 @@ def make_config(config, cut_scale: float = 1.0) -> GsRasterConfig:
     return cached
 
 
+def make_config_f64(config) -> GsRasterConfigF64:
+    """RasterConfig -> the float64 entry points' config: the thresholds keep their double values (0.99 and 1/255 as
+    floats differ from the doubles by ~1e-8 relative).  No forward_cut, tuning or stride fields."""
+    return GsRasterConfigF64(
+        int(config.tile_size), int(config.antialias), int(config.use_alpha_blending),
+        int(config.compute_point_heuristic), int(config.compute_visibility or config.compute_point_heuristic),
+        float(config.clamp_margin), float(config.blur_cov), float(config.clamp_max_alpha),
+        float(config.alpha_threshold), float(config.saturate_threshold))
+
+
 def make_shard(shard):
     """None, or a parallel.RowShard -> byref(GsRowShard) for the C-ABI."""
     if shard is None:
@@ -324,8 +358,27 @@ def require_device(*tensors: torch.Tensor, dtype=torch.float32, what="tensor") -
                 f"{what}: got a {t.device.type} tensor; taichi_gaussian_rasterizer_amd runs on a HIP device only "
                 "(there is no CPU path in the product; the CPU oracle lives in oracle/ for tests)")
         if dtype is not None and t.dtype != dtype:
-            raise TypeError(f"{what}: expected {dtype}, got {t.dtype} (the HIP kernels are float32; the reference's "
-                            "float64 instantiations exist for gradcheck only)")
+            raise TypeError(f"{what}: expected {dtype}, got {t.dtype} (the HIP kernels are float32; float64 runs in "
+                            "project_to_image, evaluate_sh_at and rasterize_with_tiles only, for gradcheck)")
+
+
+def float_dtype(*tensors: torch.Tensor, what="tensor") -> torch.dtype:
+    """The floating-point dtype of an operator call: float32, or float64 when every floating-point tensor of the call
+    is float64 (the f64 kernels exist for gradcheck).  Devices are checked first: a CPU tensor raises RuntimeError
+    whatever its dtype; a call mixing float32 and float64 raises TypeError."""
+    require_device(*tensors, dtype=None, what=what)
+    dtypes = {t.dtype for t in tensors if t is not None}
+    if dtypes == {torch.float64}:
+        return torch.float64
+    if torch.float64 in dtypes:
+        raise TypeError(f"{what}: mixes {', '.join(sorted(str(d) for d in dtypes))}; every floating-point tensor of a "
+                        "call must be float32, or every one float64")
+    require_device(*tensors, what=what)
+    return torch.float32
+
+
+def scratch(nbytes: int, device) -> torch.Tensor:
+    return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
 
 
 def ptr(t) -> c_void_p:

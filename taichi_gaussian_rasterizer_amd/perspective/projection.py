@@ -3,7 +3,8 @@
 Same operator interface as the reference perspective/projection.py:190-248 (`apply`,
 `project_to_image`): returns (points (V,7), depth (V,1), indexes (V) int64) for the Gaussians in
 view, differentiable w.r.t. position, log_scaling, rotation, alpha_logit, T_camera_world and
-projection; `indexes` is non-differentiable (:155).
+projection; `indexes` is non-differentiable (:155).  float32, or float64 when every floating-point input is float64 (the
+reference's f64 instantiation, for gradcheck: csrc/project_f64.hip).
 """
 from __future__ import annotations
 
@@ -29,8 +30,12 @@ class _ProjectFunction(torch.autograd.Function):
     @nv.on_tensor_device
     def forward(ctx, position, log_scaling, rotation, alpha_logit, T_camera_world, projection, image_size,
                 depth_range, config: RasterConfig):
-        nv.require_device(position, log_scaling, rotation, alpha_logit, T_camera_world, projection,
-                          what="project_to_image")
+        dtype = nv.float_dtype(position, log_scaling, rotation, alpha_logit, T_camera_world, projection,
+                               what="project_to_image")
+        ctx.dtype = dtype
+        if dtype == torch.float64:
+            return _forward_f64(ctx, position, log_scaling, rotation, alpha_logit, T_camera_world, projection,
+                                image_size, depth_range, config)
         lib = nv.lib()
         n = position.shape[0]
         dev = position.device
@@ -63,6 +68,8 @@ class _ProjectFunction(torch.autograd.Function):
     @staticmethod
     @nv.on_tensor_device
     def backward(ctx, dpoints, ddepth, _dindexes, _dndc):
+        if ctx.dtype == torch.float64:
+            return _backward_f64(ctx, dpoints, ddepth)
         position, log_scaling, rotation, alpha_logit, T, proj, slot_of = ctx.saved_tensors
         lib = nv.lib()
         n = position.shape[0]
@@ -86,6 +93,58 @@ class _ProjectFunction(torch.autograd.Function):
                                     nv.ptr(d_T), nv.ptr(d_proj), nv.ptr(scratch), nbytes, nv.stream()),
                  "gs_project_bwd")
         return d_pos, d_ls, d_rot, d_al, d_T, d_proj, None, None, None
+
+
+def _forward_f64(ctx, position, log_scaling, rotation, alpha_logit, T_camera_world, projection, image_size,
+                 depth_range, config):
+    """gs_project_fwd_f64: the same outputs in float64 (indexes int64)."""
+    lib = nv.lib()
+    n = position.shape[0]
+    dev = position.device
+    T, proj = T_camera_world.contiguous(), projection.contiguous()
+    points = torch.empty((n, 7), dtype=torch.float64, device=dev)
+    depth = torch.empty((n, 1), dtype=torch.float64, device=dev)
+    ndc = torch.empty((n, 1), dtype=torch.float64, device=dev)
+    indexes = torch.empty((n,), dtype=torch.int64, device=dev)
+    slot_of = torch.empty((n,), dtype=torch.int32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    nbytes = lib.gs_project_f64_scratch_bytes(n)
+    scratch = nv.scratch(nbytes, dev)
+    nv.check(lib.gs_project_fwd_f64(n, nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation), nv.ptr(alpha_logit),
+                                    nv.ptr(T), nv.ptr(proj), int(image_size[0]), int(image_size[1]),
+                                    float(depth_range[0]), float(depth_range[1]), nv.make_config_f64(config),
+                                    nv.ptr(points), nv.ptr(depth), nv.ptr(ndc), nv.ptr(indexes), nv.ptr(slot_of),
+                                    nv.ptr(count), nv.ptr(scratch), nbytes, nv.stream()), "gs_project_fwd_f64")
+    v = int(count.item())
+    points, depth, ndc, indexes = points[:v], depth[:v], ndc[:v], indexes[:v]
+    ctx.image_size = (int(image_size[0]), int(image_size[1]))
+    ctx.config = config
+    ctx.save_for_backward(position, log_scaling, rotation, alpha_logit, T, proj, slot_of)
+    ctx.mark_non_differentiable(indexes, ndc)
+    return points, depth, indexes, ndc
+
+
+def _backward_f64(ctx, dpoints, ddepth):
+    position, log_scaling, rotation, alpha_logit, T, proj, slot_of = ctx.saved_tensors
+    lib = nv.lib()
+    n = position.shape[0]
+    dev = position.device
+    need_T, need_proj = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+    d_pos, d_ls, d_rot, d_al = (torch.empty_like(t) for t in (position, log_scaling, rotation, alpha_logit))
+    d_T = torch.empty((4, 4), dtype=torch.float64, device=dev) if need_T else None
+    d_proj = torch.empty((4,), dtype=torch.float64, device=dev) if need_proj else None
+    nbytes = lib.gs_project_bwd_f64_scratch_bytes(n) if (need_T or need_proj) else 0
+    scratch = nv.scratch(nbytes, dev)
+    gp = dpoints.contiguous() if dpoints is not None else None
+    gd = ddepth.contiguous() if ddepth is not None else None
+    if nv.float_dtype(gp, gd, what="project_to_image backward") != torch.float64:
+        raise TypeError("project_to_image backward: float64 forward, float32 gradients")
+    nv.check(lib.gs_project_bwd_f64(n, nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation), nv.ptr(alpha_logit),
+                                    nv.ptr(T), nv.ptr(proj), ctx.image_size[0], ctx.image_size[1],
+                                    nv.make_config_f64(ctx.config), nv.ptr(slot_of), nv.ptr(gp), nv.ptr(gd),
+                                    nv.ptr(d_pos), nv.ptr(d_ls), nv.ptr(d_rot), nv.ptr(d_al), nv.ptr(d_T),
+                                    nv.ptr(d_proj), nv.ptr(scratch), nbytes, nv.stream()), "gs_project_bwd_f64")
+    return d_pos, d_ls, d_rot, d_al, d_T, d_proj, None, None, None
 
 
 def _check_inputs(position, log_scaling, rotation, alpha_logit, T_camera_world, projection, image_size, depth_range):

@@ -3,7 +3,8 @@
 Operator interface of the reference rasterizer/function.py:96-161: `rasterize_with_tiles`,
 `rasterize`, `RasterOut`.  image / image_weight are (H,W,F) / (H,W); image_weight, visibility and
 point_heuristic are non-differentiable (:72); gradients flow to gaussians2d and features.  Up to 32 feature channels
-run the narrow kernels, 33 to 512 the wide ones (csrc/raster_wide.hip).
+run the narrow kernels, 33 to 512 the wide ones (csrc/raster_wide.hip).  float64 splats and features (for gradcheck)
+run csrc/raster_f64.hip, up to 32 channels; `rasterize` maps their tiles from a float32 copy.
 """
 from __future__ import annotations
 
@@ -32,8 +33,10 @@ class _RasterFunction(torch.autograd.Function):
     @staticmethod
     @nv.on_tensor_device
     def forward(ctx, gaussians, features, overlap_to_point, tile_overlap_ranges, image_size, config: RasterConfig):
-        nv.require_device(gaussians, features, what="rasterize_with_tiles")
+        ctx.dtype = nv.float_dtype(gaussians, features, what="rasterize_with_tiles")
         nv.require_device(overlap_to_point, tile_overlap_ranges, dtype=torch.int32, what="rasterize_with_tiles tiles")
+        if ctx.dtype == torch.float64:
+            return _forward_f64(ctx, gaussians, features, overlap_to_point, tile_overlap_ranges, image_size, config)
         lib = nv.lib()
         dev = features.device
         w, h = int(image_size[0]), int(image_size[1])
@@ -69,6 +72,8 @@ class _RasterFunction(torch.autograd.Function):
     @staticmethod
     @nv.on_tensor_device
     def backward(ctx, grad_image, _ga, _gh, _gv):
+        if ctx.dtype == torch.float64:
+            return _backward_f64(ctx, grad_image)
         g, f, o2p, ranges, image = ctx.saved_tensors
         lib = nv.lib()
         v, F = g.shape[0], f.shape[1]
@@ -95,6 +100,58 @@ class _RasterFunction(torch.autograd.Function):
         nv.check(lib.gs_raster_bwd_unpack(v, F, nv.ptr(rows), nv.ptr(grad_g), nv.ptr(grad_f), nv.ptr(heur),
                                           nv.stream()), "gs_raster_bwd_unpack")
         return grad_g, grad_f, None, None, None, None
+
+
+def _forward_f64(ctx, gaussians, features, overlap_to_point, tile_overlap_ranges, image_size, config):
+    """gs_raster_fwd_f64 (csrc/raster_f64.hip): the reference formulas in float64, up to MAX_FEATURES channels.  The
+    forward blends each tile's whole list (RasterConfig.forward_cut does not apply)."""
+    lib = nv.lib()
+    dev = features.device
+    w, h = int(image_size[0]), int(image_size[1])
+    v, F = gaussians.shape[0], features.shape[1]
+    if F > MAX_FEATURES:
+        raise NotImplementedError(f"rasterize_with_tiles: float64 features are at most {MAX_FEATURES} wide, got {F}")
+    g, f = gaussians.contiguous(), features.contiguous()
+    o2p, ranges = overlap_to_point.contiguous(), tile_overlap_ranges.contiguous()
+    image = torch.empty((h, w, F), dtype=torch.float64, device=dev)
+    alpha = torch.empty((h, w), dtype=torch.float64, device=dev)
+    heur = torch.zeros((v if config.compute_point_heuristic else 0, 2), dtype=torch.float64, device=dev)
+    want_vis = config.compute_visibility or config.compute_point_heuristic
+    vis = torch.zeros((v if want_vis else 0,), dtype=torch.float64, device=dev)
+    nbytes = lib.gs_raster_f64_scratch_bytes(v, o2p.shape[0], F)
+    scratch = nv.scratch(nbytes, dev)
+    nv.check(lib.gs_raster_fwd_f64(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                   nv.make_config_f64(config), nv.ptr(image), nv.ptr(alpha),
+                                   nv.ptr(vis) if want_vis else None, nv.ptr(scratch), nbytes, nv.stream()),
+             "gs_raster_fwd_f64")
+    vis_out = vis if config.compute_visibility else torch.empty((0,), dtype=torch.float64, device=dev)
+    ctx.image_size, ctx.config = (w, h), config
+    ctx.heur = heur
+    ctx.mark_non_differentiable(alpha, vis_out, heur)
+    ctx.save_for_backward(g, f, o2p, ranges, image)
+    return image, alpha, heur, vis_out
+
+
+def _backward_f64(ctx, grad_image):
+    """gs_raster_bwd_f64: per-(tile, entry) records summed per splat in list order (bit-reproducible); the point
+    heuristics go into the tensor the forward returned, as in float32."""
+    g, f, o2p, ranges, image = ctx.saved_tensors
+    lib = nv.lib()
+    v, F = g.shape[0], f.shape[1]
+    w, h = ctx.image_size
+    config = ctx.config
+    gi = grad_image.contiguous()
+    if nv.float_dtype(gi, what="rasterize backward") != torch.float64:
+        raise TypeError("rasterize backward: float64 forward, float32 gradient")
+    grad_g = torch.empty_like(g)
+    grad_f = torch.empty_like(f)
+    nbytes = lib.gs_raster_f64_scratch_bytes(v, o2p.shape[0], F)
+    scratch = nv.scratch(nbytes, g.device)
+    nv.check(lib.gs_raster_bwd_f64(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                   nv.make_config_f64(config), nv.ptr(image), nv.ptr(gi), nv.ptr(grad_g),
+                                   nv.ptr(grad_f), nv.ptr(ctx.heur) if config.compute_point_heuristic else None,
+                                   nv.ptr(scratch), nbytes, nv.stream()), "gs_raster_bwd_f64")
+    return grad_g, grad_f, None, None, None, None
 
 
 def _validate(gaussians2d, features, overlap_to_point, tile_overlap_ranges, image_size, config):
@@ -141,7 +198,10 @@ def rasterize(gaussians2d: torch.Tensor, depth: torch.Tensor, features: torch.Te
     """Rasterize an image given 2d gaussians, depths (for sorting) and features."""
     assert gaussians2d.shape[0] == depth.shape[0] == features.shape[0], \
         f"Size mismatch: got {gaussians2d.shape}, {depth.shape}, {features.shape}"
+    splats = gaussians2d
+    if gaussians2d.dtype == torch.float64:  # the mapper is float32-only, as the reference's (tile_mapper.py:12)
+        splats, depth = gaussians2d.detach().float(), depth.detach().float()
     overlap_to_point, tile_overlap_ranges = map_to_tiles(
-        gaussians2d, depth, image_size=image_size, config=config, use_depth16=use_depth16)
+        splats, depth, image_size=image_size, config=config, use_depth16=use_depth16)
     return rasterize_with_tiles(gaussians2d, features, tile_overlap_ranges=tile_overlap_ranges.view(-1, 2),
                                 overlap_to_point=overlap_to_point, image_size=image_size, config=config)

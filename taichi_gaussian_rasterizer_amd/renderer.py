@@ -15,6 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _native as nv
 from .data_types import Gaussians3D, RasterConfig
 from .mapper.tile_mapper import map_to_tiles
 from .perspective.params import CameraParams
@@ -145,6 +146,16 @@ def _check_call(gaussians, camera_params, config, flags: dict) -> None:
             raise TypeError(f"{name} must be bool")
 
 
+def _refuse_float64(gaussians, camera_params) -> None:
+    """render_gaussians is float32 only (the float64 operators exist for gradcheck): refuse f64 before any launch.  A
+    CPU tensor still raises the device error first."""
+    tensors = (*gaussians.shape_tensors(), gaussians.feature, camera_params.T_camera_world, camera_params.projection)
+    if any(isinstance(t, torch.Tensor) and t.dtype == torch.float64 for t in tensors):
+        nv.require_device(*tensors, dtype=None, what="render_gaussians")
+        raise TypeError("render_gaussians: expected float32 tensors, got float64 (float64 runs in project_to_image, "
+                        "evaluate_sh_at and rasterize_with_tiles, for gradcheck)")
+
+
 def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config: RasterConfig = RasterConfig(),
                      use_sh: bool = False, render_depth: bool = False, use_depth16: bool = False,
                      render_median_depth: bool = False) -> Rendering:
@@ -154,6 +165,7 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
     _check_call(gaussians, camera_params, config, dict(use_sh=use_sh, render_depth=render_depth,
                                                       use_depth16=use_depth16,
                                                       render_median_depth=render_median_depth))
+    _refuse_float64(gaussians, camera_params)
     from .fused import fused_supported, render_fused
     if fused_supported(gaussians, camera_params, use_sh, render_median_depth):
         return render_fused(gaussians, camera_params, config, render_depth, use_depth16,
