@@ -562,6 +562,55 @@ int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, con
                       double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
                       int64_t scratch_bytes, void* stream);
 
+/* -------------------------------------------------------------------- photometric loss --
+ * (1 - ssim_weight) * mean|x - y| + ssim_weight * (1 - SSIM(x, y)) on channel-last images, x = image (the render),
+ * y = target; both (batch, height, width, channels), read through a batch, a row and a pixel stride in ELEMENTS with
+ * the channels contiguous (pixel stride >= channels, row stride >= width * pixel stride), so a channel slice or a row
+ * view of a larger buffer goes in without a copy.  SSIM: 1-D Gaussian window of odd size 3 .. 15,
+ * g[i] = exp(-(i - (ws - 1) / 2)^2 / (2 sigma^2)) normalised to sum 1 in double and rounded to the compute type, applied
+ * as g (x) g per channel with zero padding; C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ *   ssim_map = (2 mu_x mu_y + C1)(2 cov + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x + var_y + C2)).
+ * The kernels form the second moments on x - c, y - c' with per-tile pivots (csrc/loss.hip), which keeps float32
+ * accurate on smooth, flat and nearly equal images.  `valid` != 0: only pixels whose window lies inside the image enter
+ * the SSIM mean (needs height, width >= window_size); the map itself does not change.
+ *
+ * gs_ssim_window: host only; the float32 weights the kernels use.
+ * Forward: results (3, device) = [loss, mean|x - y|, mean ssim]; ssim_map (B,H,W,C) and saved_maps (3,B,H,W,C: what the
+ * backward needs) are optional (NULL).  With ssim_weight == 0 and neither map the SSIM work is skipped and results[2]
+ * is NaN.  scratch: gs_photo_loss_scratch_bytes, 8-byte aligned; the per-workgroup partial sums are added in a fixed order by a second
+ * launch, in double: the results repeat bit for bit.
+ * Backward: d_image (B,H,W,C, contiguous; written, not accumulated) =
+ *   g * (l1_coeff * d mean|x - y| / dx + ssim_coeff * d mean_ssim / dx) + sum_q upstream_map(q) * d ssim_map(q) / dx,
+ * g = *grad_loss (device scalar; NULL = 1), upstream_map (B,H,W,C) optional.  The photometric loss is
+ * l1_coeff = 1 - ssim_weight, ssim_coeff = -ssim_weight.  sign(0) = 0 in the L1 term.  saved_maps may be NULL when
+ * ssim_coeff == 0 and upstream_map == NULL.  Zero pixels: both calls are no-ops returning 0. */
+int gs_ssim_window(int32_t window_size, double sigma, float* host_out);
+int64_t gs_photo_loss_scratch_bytes(int64_t batch, int64_t height, int64_t width, int64_t channels);
+int gs_photo_loss_fwd(int64_t batch, int64_t height, int64_t width, int64_t channels, const float* image,
+                      int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                      const float* target, int64_t target_batch_stride, int64_t target_row_stride,
+                      int64_t target_pixel_stride, int32_t window_size, double sigma, double data_range,
+                      double ssim_weight, int32_t valid, float* ssim_map, float* saved_maps, void* scratch,
+                      int64_t scratch_bytes, float* results, void* stream);
+int gs_photo_loss_bwd(int64_t batch, int64_t height, int64_t width, int64_t channels, const float* image,
+                      int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                      const float* target, int64_t target_batch_stride, int64_t target_row_stride,
+                      int64_t target_pixel_stride, int32_t window_size, double sigma, int32_t valid,
+                      const float* saved_maps, const float* upstream_map, const float* grad_loss, double l1_coeff,
+                      double ssim_coeff, float* d_image, void* stream);
+int gs_photo_loss_fwd_f64(int64_t batch, int64_t height, int64_t width, int64_t channels, const double* image,
+                          int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                          const double* target, int64_t target_batch_stride, int64_t target_row_stride,
+                          int64_t target_pixel_stride, int32_t window_size, double sigma, double data_range,
+                          double ssim_weight, int32_t valid, double* ssim_map, double* saved_maps, void* scratch,
+                          int64_t scratch_bytes, double* results, void* stream);
+int gs_photo_loss_bwd_f64(int64_t batch, int64_t height, int64_t width, int64_t channels, const double* image,
+                          int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                          const double* target, int64_t target_batch_stride, int64_t target_row_stride,
+                          int64_t target_pixel_stride, int32_t window_size, double sigma, int32_t valid,
+                          const double* saved_maps, const double* upstream_map, const double* grad_loss,
+                          double l1_coeff, double ssim_coeff, double* d_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ operator API of taichi_splatting (reference taichi_splatting/__init__.py:1-33).
 Compute backend: hand-written HIP kernels for gfx950 in libgsplat_hip.so (C-ABI:
 include/gsplat_hip.h), called through ctypes.  There is no other backend.
 """
-from . import hip_lib, perspective
+from . import hip_lib, losses, perspective
 from . import hip_lib as cuda_lib  # drop-in alias for `taichi_splatting.cuda_lib`
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
@@ -41,7 +41,7 @@ __all__ = [
     'RasterConfig', 'CameraParams', 'RasterOut',
     'evaluate_sh_at',
     'rasterize', 'rasterize_with_tiles',
-    'perspective', 'hip_lib', 'cuda_lib',
+    'perspective', 'hip_lib', 'cuda_lib', 'losses',
     'TaichiQueue', 'taichi_queue',
     'install_as_taichi_splatting',
 ]

@@ -157,6 +157,16 @@ SIGNATURES = {
                                           _P]),
     "gs_raster_bwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P, _P,
                                           _I64, _P]),
+    "gs_ssim_window": (ctypes.c_int, [_I32, _F64, POINTER(c_float)]),
+    "gs_photo_loss_scratch_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "gs_photo_loss_fwd": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _F64,
+                                          _F64, _F64, _I32, _P, _P, _P, _I64, _P, _P]),
+    "gs_photo_loss_bwd": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _F64,
+                                          _I32, _P, _P, _P, _F64, _F64, _P, _P]),
+    "gs_photo_loss_fwd_f64": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32,
+                                              _F64, _F64, _F64, _I32, _P, _P, _P, _I64, _P, _P]),
+    "gs_photo_loss_bwd_f64": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32,
+                                              _F64, _I32, _P, _P, _P, _F64, _F64, _P, _P]),
 }
 
 _lib = None
@@ -219,7 +229,7 @@ class _TimedLib:
         fn = getattr(self._h, name)
         if name.endswith("_bytes") or name in ("gs_last_error", "gs_version", "gs_grad_row_floats", "gs_frame_layout",
                                                "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_part",
-                                               "gs_map_touched_offset"):
+                                               "gs_map_touched_offset", "gs_ssim_window"):
             setattr(self, name, fn)
             return fn
 

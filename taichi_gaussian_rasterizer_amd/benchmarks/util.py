@@ -27,6 +27,8 @@ FLAGS = {
     "saturate_threshold": dict(type=float, default=0.9999),
     "alpha_threshold": dict(type=float, default=1 / 255),
     "pixel_stride": dict(type=str, default="2,2"),
+    "ssim_weight": dict(type=float, default=0.2, help="weight of 1 - SSIM in the photometric loss"),
+    "json": dict(type=str, default="", help="write the benchmark's record to this file"),
 }
 _PAIRS = ("image_size", "pixel_stride")
 

@@ -18,6 +18,7 @@ from pathlib import Path
 import torch
 
 from .. import Gaussians2D, RasterConfig, rasterize
+from ..losses import photometric_loss
 from ..misc.renderer2d import point_basis, project_gaussians2d, uniform_split_gaussians2d
 from ..optim import ParameterClass, VisibilityAwareLaProp
 from ..scenes import random_2d_gaussians
@@ -38,6 +39,8 @@ def parse_args(args=None):
     p.add_argument("--prune_rate", type=float, default=0.025, help="fraction pruned per epoch, decaying to 0")
     p.add_argument("--opacity_reg", type=float, default=0.00001)
     p.add_argument("--scale_reg", type=float, default=0.1)
+    p.add_argument("--ssim_weight", type=float, default=0.0,
+                   help="0: the MSE image loss; above 0: losses.photometric_loss, (1 - w) * L1 + w * (1 - SSIM)")
     p.add_argument("--antialias", action="store_true")
     p.add_argument("--size", type=str, default="256,256", help="size of the synthetic target when no image is given")
     p.add_argument("--device", type=str, default="cuda:0")
@@ -85,7 +88,7 @@ def as_gaussians(params: ParameterClass) -> Gaussians2D:
 
 
 def train_epoch(params: ParameterClass, target: torch.Tensor, config: RasterConfig, iters: int, opacity_reg: float,
-                scale_reg: float):
+                scale_reg: float, ssim_weight: float = 0.0):
     h, w = target.shape[:2]
     raster = None
     for _ in range(iters):
@@ -94,7 +97,10 @@ def train_epoch(params: ParameterClass, target: torch.Tensor, config: RasterConf
         raster = rasterize(project_gaussians2d(gaussians), gaussians.z_depth.clamp(0, 1), gaussians.feature, (w, h),
                            config)
         size = torch.exp(gaussians.log_scaling) / min(w, h)
-        loss = (torch.nn.functional.mse_loss(raster.image.sigmoid(), target)
+        image = raster.image.sigmoid()
+        image_loss = (photometric_loss(image, target, ssim_weight=ssim_weight) if ssim_weight > 0
+                      else torch.nn.functional.mse_loss(image, target))
+        loss = (image_loss
                 + opacity_reg * gaussians.opacity.mean() + scale_reg * size.pow(2).mean())
         loss.backward()
         seen = (raster.visibility > 1e-8).nonzero().squeeze(1)
@@ -147,7 +153,8 @@ def main(args=None):
         params.set_learning_rate(position=lr)
         torch.cuda.synchronize()
         started = time.perf_counter()
-        params, raster = train_epoch(params, target, config, size, args.opacity_reg, args.scale_reg)
+        params, raster = train_epoch(params, target, config, size, args.opacity_reg, args.scale_reg,
+                                    args.ssim_weight)
         torch.cuda.synchronize()
         rate = size / (time.perf_counter() - started)
         quality = psnr(raster.image.sigmoid().detach(), target)
