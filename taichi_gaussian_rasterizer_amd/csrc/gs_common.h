@@ -142,11 +142,6 @@ struct GsCompactArgs {
 };
 int gs_map_compact_bin(const GsMapBinPlan* plan, const GsCompactArgs* c, void* stream);
 int gs_map_bin_counters(const GsMapBinPlan* plan, int64_t n, int32_t** words, int32_t* count);
-// experiment (GS_PROJECT_ONE_PASS): projection + cull + compaction + binning in ONE kernel with a decoupled look-back
-// (mapper.hip); pa = project.hip's filled gs_proj::ProjArgs, lookback = gs_map_one_pass_scratch_bytes(n) bytes
-int64_t gs_map_one_pass_scratch_bytes(int64_t n);
-int gs_map_project_compact_bin(const GsMapBinPlan* plan, const void* pa, const GsCompactArgs* c, float* camera_pos,
-                               void* lookback, void* stream);
 int gs_map_prepare_ex(int64_t v, const int32_t* v_dev, const float* points, int32_t width, int32_t height,
                       const GsRasterConfig* cfg, int64_t k_capacity, int32_t* tile_ranges, int32_t* counts_out,
                       int32_t* counts_host, int32_t* tile_order, const GsRowShard* shard, void* scratch,
@@ -289,32 +284,6 @@ __device__ __forceinline__ float gs_wave_reduce_transposed(float (&v)[N], int la
   }
   d = gs_dpp_add_full<0xB1>(d);  // quad_perm:[1,0,3,2]
   d = gs_dpp_add_full<0x4E>(d);  // quad_perm:[2,3,0,1]
-  return d;
-}
-
-// Experiment (GS_BWD_BPERMUTE in raster_bwd.hip): the two swap stages of the 8-value butterfly through the LDS crossbar
-// (ds_bpermute_b32: no LDS memory, but the LDS pipe) instead of v_permlane32/16_swap -- per register pair two selects,
-// one exchange on the other pipe and an add: 3 VALU slots where swap + add take 4.  Measured: 0.70 against 0.61 ms
-// (profiles/r3/ab_butterfly_bpermute.txt) -- six more operations per (region, splat) on the LDS pipe, which the record
-// fetches and the zero reads already use, cost far more than the six VALU slots they free.  Not used.
-__device__ __forceinline__ float gs_wave_reduce_transposed8_bpermute(float (&v)[8], int lane) {
-  const bool up32 = (lane & 32) != 0, up16 = (lane & 16) != 0;
-  const int addr32 = (lane ^ 32) << 2, addr16 = (lane ^ 16) << 2;
-  float a[4], b[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float keep = up32 ? v[i + 4] : v[i], send = up32 ? v[i] : v[i + 4];
-    a[i] = keep + __int_as_float(__builtin_amdgcn_ds_bpermute(addr32, __float_as_int(send)));
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const float keep = up16 ? a[i + 2] : a[i], send = up16 ? a[i] : a[i + 2];
-    b[i] = keep + __int_as_float(__builtin_amdgcn_ds_bpermute(addr16, __float_as_int(send)));
-  }
-  const float t = gs_dpp_add_full<0x128>(b[0]), u = gs_dpp_add_full<0x128>(b[1]);  // row_ror:8
-  float d = gs_dpp_add_full<0x141>((lane & 8) != 0 ? u : t);                      // row_half_mirror
-  d = gs_dpp_add_full<0xB1>(d);                                                   // quad_perm:[1,0,3,2]
-  d = gs_dpp_add_full<0x4E>(d);                                                   // quad_perm:[2,3,0,1]
   return d;
 }
 

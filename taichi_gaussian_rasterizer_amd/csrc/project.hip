@@ -357,19 +357,6 @@ int gs_project_fwd_ex(int64_t n, const float* position, const float* log_scaling
   int* counts = reinterpret_cast<int*>(base + gs_align_up(n * 32, 256));
   int* offsets = counts + gs_align_up(int64_t(nb + 1) * 4, 256) / 4;
   void* scan_scratch = offsets + gs_align_up(int64_t(nb + 1) * 4, 256) / 4;
-#ifdef GS_PROJECT_ONE_PASS
-  if (bin) {
-    GsCompactArgs c;
-    c.n = n; c.st_rows = nullptr; c.block_counts = nullptr;
-    c.block_offsets = GS_PROJECT_ONE_PASS == 2 ? reinterpret_cast<const int*>(1) : nullptr;  // 2: count + recompute
-    c.num_blocks = nb; c.inv_far = a.inv_far; c.ndc_denom = a.ndc_denom;
-    c.points = points; c.depth = depth; c.ndc = ndc_depth; c.indexes = indexes; c.slot_of = slot_of;
-    c.num_visible = num_visible; c.depth_feat = depth_features; c.depth_feat_stride = depth_features_stride;
-    c.zero_rows = zero_rows; c.zero_row_v4 = zero_row_floats / 4;
-    GS_REQUIRE(scratch_bytes >= gs_map_one_pass_scratch_bytes(n), GS_ERR_SCRATCH_TOO_SMALL, "gs_project_fwd: scratch");
-    return gs_map_project_compact_bin(bin, &a, &c, camera_pos, scratch, stream);
-  }
-#endif
   int32_t* zero_words = nullptr;
   int32_t zero_count = 0;
   if (bin)

@@ -1,11 +1,9 @@
 // project_math.h -- the projection's per-Gaussian device arithmetic (perspective/projection.py:32-80, math in
-// taichi_lib/generic.py:96-158, :217-237, :419-427), shared by project.hip (the two-pass projection and the adjoint) and
-// by mapper.hip's one-pass project + compact + bin kernel (frame calls).
+// taichi_lib/generic.py:96-158, :217-237, :419-427), used by project.hip (the two-pass projection and the adjoint).
 //
-// Both must produce the SAME BITS -- tests compare the frame calls with the composed operators bit for bit -- while
-// mapper.hip is compiled with -ffp-contract=off (its grid query matches the CPU oracle op for op) and project.hip with
-// hipcc's default (fast).  The functions below therefore pin their own contraction mode: `#pragma clang fp contract(fast)`
-// at the head of each body, whatever the translation unit's flag says.
+// The functions below pin their own contraction mode -- `#pragma clang fp contract(fast)` at the head of each body,
+// hipcc's default -- so that they produce the same bits whatever the including translation unit's flag says (mapper.hip,
+// compiled with -ffp-contract=off, once ran them in a one-pass projection kernel: DESIGN 5).
 #pragma once
 #include "gs_common.h"
 #include "../../include/gs_detmath.h"

@@ -58,17 +58,13 @@ __device__ __forceinline__ void tile_origin(const BwdArgs& a, int tile, int& x0,
   yout0 = lty * a.tile_size;
 }
 
-#ifndef GS_BWD_WAVES
-#define GS_BWD_WAVES 1  // minimum waves per SIMD requested from the register allocator (1 = no constraint)
-#endif
-
 // LDS arena of one wave: sized by the 64-splat staging group, not by the wave's pixel region
 // MODE 0: lean (6 ellipse-frame moments); 1: lean + the two densification heuristics (training with statistics);
 // 2: full (7 gradients + 2 heuristics per pixel; antialiased pdf)
 template <int FP, int MODE>
 struct BwdShape {
   static constexpr bool FULL = MODE == 2;
-  static constexpr int NS = MODE == 2 ? 9 : MODE == 1 ? 8 : 6;
+  static constexpr int NS = MODE == 2 ? 9 : MODE == 1 ? 8 : 6;  // sums per splat besides the F feature gradients
   static constexpr int NACC = NS + FP;           // values reduced per splat
   static constexpr int ROW = ((9 + FP + 15) / 16) * 16;
   static constexpr int GEO_V4 = FULL ? 3 : 2;     // float4s of geometry per staged record ...
@@ -79,66 +75,39 @@ struct BwdShape {
   static constexpr int ARENA_F = (REC_F + ACC_F) > OUT_F ? (REC_F + ACC_F) : OUT_F;
 };
 
-// The wave sum of the 9 per-splat values.  0 (shipped): the transposed register butterfly.  1 / 2 (round-3 experiments,
-// kept buildable: tools/build_variant.sh lds2 raster_bwd -DGS_BWD_LDS_REDUCE=2): 8 of the values transposed through LDS
-// in one 8-row pass / two 4-row passes.  In tools/ubench/mfma_reduce.hip, beside 80 plain v_fma, the LDS form costs
-// 57 ns per call against 87 ns for the butterfly -- but in THIS kernel it is slower (0.67 vs 0.64 ms at C3, 6 waves per
-// SIMD either way): the kernel already reads three b128 records per splat from LDS, and 8 ds_write_b32 + 2 ds_read_b128
-// + 2 result writes more per (tile, splat) put the CU's LDS array at ~170 of the ~200 cycles four SIMDs spend on a
-// splat -- the reduction leaves the VALU port only to queue at the LDS.  (v1, one pass with 8 rows, also costs a wave of
-// occupancy: 1.167 vs 1.137 ms per frame.)
-// The per-splat sums start at zero.  Written as `= 0.0f` the first evaluated sub-block of the unrolled chain initialises
-// them for free -- and every splat whose first sub-block is masked out pays 9 v_mov_b32 (about 5 issue slots per
-// overlap on average, in a kernel bound by VALU issue).  1: the zeros come from LDS instead -- ceil(NACC / 4) ds_read_b128
-// of a 64-byte block of zeros at the head of every splat, on the LDS pipe, their latency under the first sub-block's
-// coordinate / exponent arithmetic -- and every sub-block accumulates.  (Kernels with up to 16 sums per splat.)
-#ifndef GS_BWD_ZERO_LDS
-#define GS_BWD_ZERO_LDS 1
-#endif
-// The sub-block masks of the staged splats as four 64-bit ballots in scalar registers (bit j of ballot b: splat j reaches
-// sub-block b, and b is still live): the walk tests them with scalar bit tests only -- no v_readfirstlane per splat, and
-// the branch no longer waits for the splat's LDS record.
-// The ninth of the nine per-splat sums does not fit the 8-value butterfly; it went through six fused DPP adds to row 3
-// (gs_wave_reduce_transposed<9>).  1: four DPP adds leave every lane with its ROW's sum, and one lane per row adds that
-// to the splat's total in LDS (ds_add_f32, four lanes on one address): two DPP adds, a move and a select less on the
-// VALU port per (region, splat).  (Ending the 8-value butterfly the same way, two DPP stages early -- 32 lanes adding
-// four partial sums per value -- is ruinous: 1.05 against 0.62 ms, profiles/r3/ab_butterfly_quarter_lds_add.txt; an LDS
-// float add costs by the lane.)
-#ifndef GS_BWD_NINTH_LDS
-#define GS_BWD_NINTH_LDS 1
-#endif
-#ifndef GS_BWD_BPERMUTE
-#define GS_BWD_BPERMUTE 0
-#endif
-#ifndef GS_BWD_HIT_EXEC
-#define GS_BWD_HIT_EXEC 1
-#endif
-#ifndef GS_BWD_MASK_BALLOTS
-#define GS_BWD_MASK_BALLOTS 1
-#endif
-#ifndef GS_BWD_FETCH_AHEAD
-#define GS_BWD_FETCH_AHEAD 1
-#endif
-#ifndef GS_BWD_LDS_REDUCE
-#define GS_BWD_LDS_REDUCE 0
-#endif
-constexpr int TR_STRIDE = GS_BWD_LDS_REDUCE == 1 ? 68 : 64;  // floats per value row of the transposition buffer
-constexpr int TR_ROWS = GS_BWD_LDS_REDUCE == 1 ? 8 : 4;
-// 3: hybrid -- values 0..3 in ONE 4-row LDS pass, values 4..8 through the 5-value butterfly
-
+// How a wave walks one staged splat.  The kernel is bound by VALU issue, so each step hands what it can to a unit that
+// has time; what was measured against each choice is recorded in DESIGN 4 and profiles/r3/.
+//   * The per-splat sums start as zeros READ FROM LDS: ceil(NACC / 4) ds_read_b128 of a 64-byte block of zeros at the
+//     head of every splat, their latency under the first sub-block's coordinate / exponent arithmetic, and every
+//     sub-block accumulates.  (Kernels with up to 16 sums per splat.  Lost: `= 0.0f`, which costs nine v_mov_b32 whenever
+//     the first sub-block is masked out -- profiles/r3/ab_zero_sums_from_lds.txt.)
+//   * The sub-block masks of the staged splats are four 64-bit ballots in scalar registers (bit j of ballot b: splat j
+//     reaches sub-block b, and b is still live): the walk tests them with scalar bit tests only, and its branches do
+//     not wait for the splat's LDS record.  (Lost: the mask as a word of the record, made scalar with a
+//     v_readfirstlane per splat -- profiles/r3/ab_mask_ballots_bwd.txt.)
+//   * The next splat's record is fetched in front of the wave reduction, into the registers of the record just used.
+//     (Lost: the fetch at the head of the iteration -- profiles/r3/ab_fetch_ahead.txt.)
+//   * Everything behind the hit test runs under EXEC = the pixels that take something from the splat; nobody adds
+//     zeros.  (Lost: a select that zeroed alpha for the other pixels, and a wave-level "nobody hit" branch in front --
+//     profiles/r3/ab_hit_under_exec.txt, ab_hit_exec_no_wave_branch.txt.)
+//   * The wave sum is the transposed register butterfly (gs_common.h).  Of nine sums (lean, F = 3) the ninth does not
+//     fit the 8-value butterfly: four DPP adds leave every lane with its ROW's sum, and one lane per row adds that to
+//     the splat's total in LDS (ds_add_f32, four lanes on one address; the Makefile keeps it one instruction).  (Lost:
+//     six DPP adds to row 3 -- ab_ninth_value_lds_add.txt; the reduction transposed through LDS in one, two or half a
+//     pass -- ubench_mfma_reduce.txt, kernel_table_lds_reduce_v2.txt, ab_hybrid_reduce.txt; the butterfly ending in a
+//     32-lane ds_add_f32 -- ab_butterfly_quarter_lds_add.txt; its swap stages through the LDS crossbar -- the last
+//     "not kept" entry of that list in DESIGN 4.)
 template <int NB, int FP, int MODE>
 __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int x0, int y0, int yout0, float* smem,
-                                                float* s_tr) {
+                                                const float* s_zeros) {
   const int lane = threadIdx.x;
   constexpr bool FULL = MODE == 2, HEUR = MODE == 1;
-  constexpr int NS = MODE == 2 ? 9 : MODE == 1 ? 8 : 6;  // sums per splat besides the F feature gradients
-  constexpr int NACC = NS + FP;           // values reduced per splat
-  constexpr int ROW = ((9 + FP + 15) / 16) * 16;
 
   // One LDS arena per wave.  The staged records (geo, feat) and the per-splat totals (acc) are dead
   // by the time the gradient rows (out) are written, so `out` aliases them: ~7.4 KB per wave
   // instead of ~11.5 KB, i.e. 21 instead of 13 resident waves per CU.
   typedef BwdShape<FP, MODE> Shape;
+  constexpr int NS = Shape::NS, NACC = Shape::NACC, ROW = Shape::ROW;
   constexpr int GEO_V4 = Shape::GEO_V4, REC_V4 = Shape::REC_V4, ACC_STRIDE = Shape::ACC_STRIDE;
   constexpr int OUT_STRIDE = Shape::OUT_STRIDE;
   float4(*s_geo)[REC_V4] = reinterpret_cast<float4(*)[REC_V4]>(smem);
@@ -146,7 +115,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
   float(*s_out)[OUT_STRIDE] = reinterpret_cast<float(*)[OUT_STRIDE]>(smem);
 
   // which value of the per-splat reduction this lane ends up owning (lane-constant; -1 = none)
-  constexpr bool NINTH_LDS = GS_BWD_NINTH_LDS && NACC == 9 && !GS_BWD_LDS_REDUCE;
+  constexpr bool NINTH_LDS = NACC == 9;
   constexpr int NBUTTERFLY = NINTH_LDS ? 8 : (NACC <= 16 ? NACC : 1);
   const int my_slot = (NACC <= 16 && (lane & 3) == 0) ? gs_reduce_slot<NBUTTERFLY>(lane) : -1;
   const int lx = lane & 7, ly = lane >> 3;
@@ -185,7 +154,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
   constexpr float K_EXP = 0.84932180028801904f;  // sqrt(0.5 * log2(e))
   constexpr float IK = 1.0f / K_EXP, IK2 = IK * IK;
 
-  int zero_off = 0;  // see GS_BWD_ZERO_LDS
+  int zero_off = 0;  // byte offset of the zeros read at the head of every splat (see above)
   for (int g0 = range_x; g0 < range_y; g0 += 64) {
     // all pixels of the region saturated -> nothing further contributes (backward.py:116-118)
     // ... and a saturated 8x8 sub-block takes no gradient from here on (:160,166): masked out before its alphas
@@ -265,27 +234,22 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
           if (4 * q + k < FP) feat[4 * q + k] = fv[k];
       }
     };
-    if (GS_BWD_FETCH_AHEAD) fetch_record(0);
+    fetch_record(0);
     uint64_t reach[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
-      reach[b] = (GS_BWD_MASK_BALLOTS && ((live >> b) & 1)) ? __ballot((staged_mask >> b) & 1) : 0ull;
+      reach[b] = ((live >> b) & 1) ? __ballot((staged_mask >> b) & 1) : 0ull;
     for (int j = 0; j < cnt; ++j) {
-      if (!GS_BWD_FETCH_AHEAD) fetch_record(j);
       int mask = 0;
-      if (GS_BWD_MASK_BALLOTS) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) mask |= int((reach[b] >> j) & 1ull) << b;
-      } else {
-        mask = __builtin_amdgcn_readfirstlane(__float_as_int(g1v.w)) & live;
-      }
+      for (int b = 0; b < NB; ++b) mask |= int((reach[b] >> j) & 1ull) << b;
 
       float S[NS], gf[FP];
-      if (GS_BWD_ZERO_LDS && !GS_BWD_LDS_REDUCE && NACC <= 16) {
+      if (NACC <= 16) {
         // (an opaque byte OFFSET, carried across the loop: an opaque pointer would lose its address space and become a
         // flat load; re-initialising it per splat would cost the v_mov this is about)
         asm volatile("" : "+v"(zero_off));
-        const float4* zp = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_tr) + zero_off);
+        const float4* zp = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_zeros) + zero_off);
         float z[16];
 #pragma unroll
         for (int q = 0; q < (NACC + 3) / 4; ++q) {
@@ -302,8 +266,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
 #pragma unroll
         for (int c = 0; c < FP; ++c) gf[c] = 0.0f;
       }
-      bool any_grad = false;  // wave-uniform: some pixel of some sub-block took a gradient from this splat
-      uint64_t hit_lanes = 0ull;
+      uint64_t hit_lanes = 0ull;  // the pixels, of any sub-block, that took a gradient from this splat
 
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
@@ -350,17 +313,11 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
         const bool over = alpha_raw > a.thr, open = Tr[b] > tsat;
         const bool hit = over && open;  // backward.py:160,166
         // (two ballots of plain compares and a scalar AND: a ballot of the conjunction is rebuilt through a VGPR)
-        if (GS_BWD_HIT_EXEC) {
-          hit_lanes |= __ballot(over) & __ballot(open);  // scalar; the EXEC-masked block below skips itself when empty
-        } else {
-          if ((__ballot(over) & __ballot(open)) == 0ull) continue;
-          any_grad = true;
-        }
+        hit_lanes |= __ballot(over) & __ballot(open);  // scalar; the EXEC-masked block below skips itself when empty
         // Everything below is linear in the pixel's alpha and touches nothing but the lane's own sums and state: it runs
         // under EXEC = the pixels that take something from this splat (a partly empty EXEC costs a wave64 instruction
-        // nothing extra), which saves the select that used to zero alpha for the others.  (GS_BWD_HIT_EXEC = 0: the select.)
-        if (GS_BWD_HIT_EXEC && !hit) continue;
-        const float a_hit = GS_BWD_HIT_EXEC ? alpha_raw : (hit ? alpha_raw : 0.0f);
+        // nothing extra), so nobody has to zero alpha for the others.
+        if (!hit) continue;
         if (FULL && a.aa) {  // aa_gradients: see the value half above
           const float d0 = s_sig_slope(aa_z[0], aa_a[0]), d1 = s_sig_slope(aa_z[1], aa_a[1]);
           const float d2 = s_sig_slope(aa_z[2], aa_a[2]), d3 = s_sig_slope(aa_z[3], aa_a[3]);
@@ -375,7 +332,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
           day = __builtin_fmaf(Px, dy, -(Py * dx));
           // dmx, dmy: the wave totals of aag Px, aag Py are rotated out of the frame once per splat (epilogue)
         }
-        const float alc = __builtin_amdgcn_fmed3f(a_hit, a.cmax, -1.0f);  // min(alpha, cmax), one v_med3_f32 (:169)
+        const float alc = __builtin_amdgcn_fmed3f(alpha_raw, a.cmax, -1.0f);  // min(alpha, cmax), one v_med3_f32 (:169)
         float dot = 0.0f;
 #pragma unroll
         for (int c = 0; c < FP; ++c) dot += feat[c] * gpix[b][c];
@@ -384,8 +341,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
         // T and R are updated so that both updates happen in place (no register copies at the end of the block).
         const float num = Tr[b] * dot - R[b];
         const float w = alc * Tr[b];
-        float alpha_grad = num * gs_rcp_fast(1.0f - alc);
-        if (!GS_BWD_HIT_EXEC && (FULL || HEUR)) alpha_grad = hit ? alpha_grad : 0.0f;  // used without the a_hit factor
+        const float alpha_grad = num * gs_rcp_fast(1.0f - alc);
 #pragma unroll
         for (int c = 0; c < FP; ++c) gf[c] += w * gpix[b][c];  // :201
         if (FULL) {
@@ -409,7 +365,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
         } else {
           // moments in the (scaled) ellipse frame (tx, ty are O(1): no cancellation for elongated splats), carrying
           // the splat's opacity: G = alpha_p * pdf * dL/dalpha
-          const float G = a_hit * alpha_grad;
+          const float G = alpha_raw * alpha_grad;
           const float Gtx = G * tx, Gty = G * ty;
           S[0] += G;
           S[1] += Gtx; S[2] += Gty;
@@ -432,92 +388,12 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
       // The record's registers are dead from here to the end of the iteration: the next splat's record is fetched into
       // them NOW, so that its LDS latency passes under the reduction below instead of in front of the next splat's
       // first instruction (no second register set, no copies).
-      if (GS_BWD_FETCH_AHEAD) fetch_record(min(j + 1, 63));
+      fetch_record(min(j + 1, 63));
       // reduce over the wave only if some pixel took a gradient (backward.py:204)
-      if (GS_BWD_HIT_EXEC) any_grad = hit_lanes != 0ull;
-      if (any_grad) {
+      if (hit_lanes != 0ull) {
         // transposed butterfly over the wave, sized for the exact number of values; the lane that ends
         // up owning value k stores it (one ds_write_b32 for all values of a chunk)
-        if (GS_BWD_LDS_REDUCE == 3 && NACC == 9) {
-          float vals[9];
-#pragma unroll
-          for (int c = 0; c < 9; ++c) vals[c] = c < NS ? S[c < NS ? c : 0] : gf[c >= NS ? c - NS : 0];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) s_tr[c * TR_STRIDE + lane] = vals[c];
-          float w5[5];
-#pragma unroll
-          for (int c = 0; c < 5; ++c) w5[c] = vals[4 + c];
-          const float tot5 = gs_wave_reduce_transposed<5>(w5, lane);
-          const int slot5 = (lane & 3) == 0 ? gs_reduce_slot<5>(lane) : -1;
-          __syncthreads();
-          const float4 u = *reinterpret_cast<const float4*>(s_tr + (lane >> 4) * TR_STRIDE + (lane & 15) * 4);
-          float t = (u.x + u.y) + (u.z + u.w);
-          t = gs_dpp_add_full<0xB1>(t);
-          t = gs_dpp_add_full<0x4E>(t);
-          t = gs_dpp_add_full<0x141>(t);
-          t = gs_dpp_add_full<0x128>(t);
-          if ((lane & 15) == 0) s_acc[j][lane >> 4] = t;
-          if (slot5 >= 0) s_acc[j][4 + slot5] = tot5;
-          __syncthreads();
-        } else if (GS_BWD_LDS_REDUCE == 2 && NACC == 9) {
-          // experiment (see GS_BWD_LDS_REDUCE above): in two passes of four values every lane stores its partial sums
-          // as rows (value, lane), lane (c = lane >> 4, s = lane & 15) adds columns 4 s .. 4 s + 3 of row c -- one
-          // conflict-free ds_read_b128 -- and four DPP adds fold the sixteen lanes of a value.  2 x (3 adds + 4 DPP) +
-          // the ninth value's six DPP adds against ~58 issue slots; the wave's own LDS accesses execute in order, so
-          // only the compiler needs the fences.
-          float vals[9];
-#pragma unroll
-          for (int c = 0; c < 9; ++c) vals[c] = c < NS ? S[c < NS ? c : 0] : gf[c >= NS ? c - NS : 0];
-          float x = vals[8];
-          x = gs_dpp_add_full<0x128>(x);
-          x = gs_dpp_add_full<0x124>(x);
-          x = gs_dpp_add_full<0x122>(x);
-          x = gs_dpp_add_full<0x121>(x);
-          x = gs_dpp_add_full<0x142>(x);
-          x = gs_dpp_add_full<0x143>(x);
-          if (lane == 60) s_acc[j][8] = x;
-#pragma unroll
-          for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) s_tr[c * TR_STRIDE + lane] = vals[4 * pass + c];
-            __syncthreads();
-            const float4 u = *reinterpret_cast<const float4*>(s_tr + (lane >> 4) * TR_STRIDE + (lane & 15) * 4);
-            float t = (u.x + u.y) + (u.z + u.w);
-            t = gs_dpp_add_full<0xB1>(t);   // quad_perm:[1,0,3,2]
-            t = gs_dpp_add_full<0x4E>(t);   // quad_perm:[2,3,0,1]
-            t = gs_dpp_add_full<0x141>(t);  // row_half_mirror
-            t = gs_dpp_add_full<0x128>(t);  // row_ror:8: all sixteen lanes of the row hold the value's total
-            if ((lane & 15) == 0) s_acc[j][4 * pass + (lane >> 4)] = t;
-            __syncthreads();
-          }
-        } else if (GS_BWD_LDS_REDUCE == 1 && NACC == 9) {
-          // Transposed through LDS instead of the register butterfly: every lane stores its 8 partial sums (row c =
-          // value c, column = lane), then lane (c = lane >> 3, s = lane & 7) adds columns 8 s .. 8 s + 7 of row c and
-          // three DPP adds fold the eight lanes of a value.  7 adds + 3 DPP against ~42 issue slots of swaps and DPP;
-          // the wave's own LDS accesses execute in order, so nothing but the compiler needs a fence.
-          float vals[9];
-#pragma unroll
-          for (int c = 0; c < 9; ++c) vals[c] = c < NS ? S[c < NS ? c : 0] : gf[c >= NS ? c - NS : 0];
-#pragma unroll
-          for (int c = 0; c < 8; ++c) s_tr[c * TR_STRIDE + lane] = vals[c];
-          float x = vals[8];
-          x = gs_dpp_add_full<0x128>(x);
-          x = gs_dpp_add_full<0x124>(x);
-          x = gs_dpp_add_full<0x122>(x);
-          x = gs_dpp_add_full<0x121>(x);
-          x = gs_dpp_add_full<0x142>(x);
-          x = gs_dpp_add_full<0x143>(x);
-          __syncthreads();
-          const float4* rowp = reinterpret_cast<const float4*>(s_tr + (lane >> 3) * TR_STRIDE + (lane & 7) * 8);
-          const float4 u0 = rowp[0], u1 = rowp[1];
-          float t = ((u0.x + u0.y) + (u0.z + u0.w)) + ((u1.x + u1.y) + (u1.z + u1.w));
-          t = gs_dpp_add_full<0xB1>(t);   // quad_perm:[1,0,3,2]
-          t = gs_dpp_add_full<0x4E>(t);   // quad_perm:[2,3,0,1]
-          t = gs_dpp_add_full<0x141>(t);  // row_half_mirror: the other quad of the 8-lane group
-          if ((lane & 7) == 0) s_acc[j][lane >> 3] = t;
-          if (lane == 60) s_acc[j][8] = x;
-          __syncthreads();
-        } else if (NINTH_LDS) {
+        if (NINTH_LDS) {
           float w8[8];
 #pragma unroll
           for (int c = 0; c < 8; ++c) w8[c] = c < NS ? S[c < NS ? c : 0] : gf[c >= NS ? c - NS : 0];
@@ -526,8 +402,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
           x = gs_dpp_add_full<0x124>(x);  // row_ror:4
           x = gs_dpp_add_full<0x122>(x);  // row_ror:2
           x = gs_dpp_add_full<0x121>(x);  // row_ror:1 -> every lane holds its row's sum
-          const float tot = GS_BWD_BPERMUTE ? gs_wave_reduce_transposed8_bpermute(w8, lane)
-                                            : gs_wave_reduce_transposed<8>(w8, lane);
+          const float tot = gs_wave_reduce_transposed<8>(w8, lane);
           if (my_slot >= 0) s_acc[j][my_slot] = tot;
           if ((lane & 15) == 0)
             __hip_atomic_fetch_add(&s_acc[j][8], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // 0 at staging
@@ -625,13 +500,11 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
 
 // Block -> work: see raster_fwd_kernel (the mapper's fullest tiles get one workgroup per 8x8 quadrant).
 template <int NB, int FP, int MODE>
-__global__ __launch_bounds__(64, GS_BWD_WAVES) void raster_bwd_kernel(const BwdArgs a) {
+__global__ __launch_bounds__(64) void raster_bwd_kernel(const BwdArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[BwdShape<FP, MODE>::ARENA_F];
-  // transposition buffer of the lean F = 3 reduction (the only shape that uses it)
-  // (GS_BWD_ZERO_LDS, butterfly reduction: the same pointer carries the 64-byte block of zeros instead)
-  __shared__ __attribute__((aligned(16))) float s_tr_buf[(GS_BWD_LDS_REDUCE && FP == 3 && MODE == 0) ? TR_ROWS * TR_STRIDE + 16 : 16];
-  float* s_tr = s_tr_buf;
-  if (GS_BWD_ZERO_LDS && !GS_BWD_LDS_REDUCE && threadIdx.x < 16) s_tr_buf[threadIdx.x] = 0.0f;  // read after the first staging barrier
+  // the 64-byte block of zeros that every splat's sums start from (raster_bwd_body)
+  __shared__ __attribute__((aligned(16))) float s_zeros[16];
+  if (threadIdx.x < 16) s_zeros[threadIdx.x] = 0.0f;  // read after the first staging barrier
   const int per_tile = a.sub_x * a.sub_y;
   constexpr int RW = NB == 1 ? 8 : 16, RH = NB == 4 ? 16 : 8;  // the wave's pixel region: NB 8x8 sub-blocks
   int tile, quad;
@@ -643,7 +516,7 @@ __global__ __launch_bounds__(64, GS_BWD_WAVES) void raster_bwd_kernel(const BwdA
       int x0, y0, yout0;
       tile_origin(a, tile, x0, y0, yout0);
       x0 += (b & 1) * 8; y0 += ((b >> 1) & 1) * 8; yout0 += ((b >> 1) & 1) * 8;
-      if (x0 < a.W && y0 < a.H) raster_bwd_body<1, FP, MODE>(a, tile, x0, y0, yout0, smem, s_tr);
+      if (x0 < a.W && y0 < a.H) raster_bwd_body<1, FP, MODE>(a, tile, x0, y0, yout0, smem, s_zeros);
       return;
     }
     const int c = b - 4 * heavy, rank = heavy + c / per_tile;
@@ -660,7 +533,7 @@ __global__ __launch_bounds__(64, GS_BWD_WAVES) void raster_bwd_kernel(const BwdA
   tile_origin(a, tile, x0, y0, yout0);
   x0 += (quad % a.sub_x) * RW; y0 += (quad / a.sub_x) * RH; yout0 += (quad / a.sub_x) * RH;
   if (x0 >= a.W || y0 >= a.H) return;
-  raster_bwd_body<NB, FP, MODE>(a, tile, x0, y0, yout0, smem, s_tr);
+  raster_bwd_body<NB, FP, MODE>(a, tile, x0, y0, yout0, smem, s_zeros);
 }
 
 template <int NB, int MODE>

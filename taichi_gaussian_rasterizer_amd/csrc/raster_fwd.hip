@@ -65,9 +65,6 @@ __device__ __forceinline__ void tile_origin(const FwdArgs& a, int tile, int& x0,
 // (Measured with it and not kept: the blend code twice, with and without the v_med3_f32 of min(alpha, clamp_max_alpha)
 // -- which can only bite when the splat's opacity exceeds the clamp -- and a scalar branch per splat on a ballot of
 // (opacity > clamp): 0.258 against 0.215 ms; four copies of the blend code undo the two-register-set pipeline.)
-#ifndef GS_FWD_MASK_BALLOTS
-#define GS_FWD_MASK_BALLOTS 1
-#endif
 template <int NB, int FP, int MODE>
 __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int x0, int y0, int yout0,
                                                 float4 (*s_geo)[(MODE == 2 ? 3 : 2) + (FP + 3) / 4], float* s_vis,
@@ -187,21 +184,21 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
           if (4 * q + k < FP) r.f[4 * q + k] = fv[k];
       }
     };
-    // GS_FWD_MASK_BALLOTS: the staged splats' sub-block masks as four scalar ballots (see raster_bwd.hip)
+    // the staged splats' sub-block masks as four scalar ballots (see raster_bwd.hip)
     uint64_t reach[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
-      reach[b] = (GS_FWD_MASK_BALLOTS && ((live >> b) & 1)) ? __ballot((staged_mask >> b) & 1) : 0ull;
+      reach[b] = ((live >> b) & 1) ? __ballot((staged_mask >> b) & 1) : 0ull;
     auto blend_splat = [&](int j, const Rec& r) {
       const float4 g0v = r.g0, g1v = r.g1, g2v = FULL ? r.g2 : make_float4(0, 0, 0, 0);
       const float(&feat)[FP] = r.f;
       int mask = 0;
-      if (GS_FWD_MASK_BALLOTS) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) mask |= int((reach[b] >> j) & 1ull) << b;
-      } else {
-        mask = __builtin_amdgcn_readfirstlane(__float_as_int(g1v.w)) & live;
-      }
+      for (int b = 0; b < NB; ++b) mask |= int((reach[b] >> j) & 1ull) << b;
+      // (`live` is already folded into the ballots.  Naming it keeps it in this lambda's closure: without the capture the
+      // compiler numbers the kernel's VGPRs differently -- same instructions -- and the generated code is held
+      // byte-identical across source clean-ups: profiles/prune/isa_identity.txt)
+      (void)live;
       float vis_sum = 0.0f;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {

@@ -43,7 +43,7 @@ __device__ __forceinline__ void s_sig_parts(float z, float& a, float& d) {
   d = __builtin_fmaf(0.21f, z2, 1.6f) * (a * (1.0f - a));
 }
 // ... in two halves: the value alone decides whether a pixel takes anything from the splat; the derivative is only
-// formed for the pixels that do (GS_BWD_HIT_EXEC: under their EXEC mask, skipped when the sub-block has none)
+// formed for the pixels that do (raster_bwd.hip: under their EXEC mask, skipped when the sub-block has none)
 __device__ __forceinline__ float s_sig_value(float z) {
   const float e = gs_exp2_fast(z * __builtin_fmaf(-0.07f * 1.44269504088896341f, z * z, -1.6f * 1.44269504088896341f));
   return gs_rcp_fast(1.0f + e);
