@@ -129,6 +129,22 @@ int gs_project_bwd(int64_t n, int64_t v, const float* position, const float* log
                    float* d_alpha_logit, float* d_T_camera_world, float* d_projection, void* scratch,
                    int64_t scratch_bytes, void* stream);
 
+/* Row-compact projection adjoint (no reference counterpart: sparse visible-row gradients): gs_project_bwd for the v
+ * visible rows only.  indexes (v) int64: the visible list of gs_project_fwd (ascending, distinct); the upstream
+ * gradients are read at row i (same striding rules), the four gradients are written to ROW i of d_position (v,3),
+ * d_log_scaling (v,3), d_rotation (v,4), d_alpha_logit (v,1) -- nothing is written for the culled Gaussians, and row i
+ * holds the bits gs_project_bwd writes to row indexes[i].  d_T_camera_world / d_projection as in gs_project_bwd
+ * (per-block partials of the visible rows, summed in a fixed order; zeros for v == 0).
+ * scratch: gs_project_bwd_rows_scratch_bytes(v), unused when both camera outputs are NULL. */
+int64_t gs_project_bwd_rows_scratch_bytes(int64_t v);
+int gs_project_bwd_rows(int64_t n, int64_t v, const float* position, const float* log_scaling, const float* rotation,
+                        const float* alpha_logit, const float* T_camera_world, const float* projection, int32_t width,
+                        int32_t height, const GsRasterConfig* cfg, const int64_t* indexes, const float* grad_points,
+                        int32_t grad_points_stride, const float* grad_depth, const float* grad_depth_sq,
+                        int32_t grad_depth_stride, float* d_position, float* d_log_scaling, float* d_rotation,
+                        float* d_alpha_logit, float* d_T_camera_world, float* d_projection, void* scratch,
+                        int64_t scratch_bytes, void* stream);
+
 /* replaces: CameraParams.camera_position (perspective/params.py:76-78, torch.inverse(T)[0:3,3]) for an
  * affine camera matrix (last row 0 0 0 1), computed on the device without a host round trip. */
 int gs_camera_position(const float* T_camera_world, float* camera_pos, void* stream);
@@ -195,6 +211,14 @@ int gs_sh_bwd(int64_t n, int64_t v, int32_t channels, int32_t degree, const floa
               const int64_t* indexes, int32_t indexes_unique, const int32_t* slot_of, const float* camera_pos,
               const float* grad_out, int32_t grad_out_stride, const float* fwd_out, int32_t fwd_out_stride,
               float* d_params, float* d_positions, float* d_camera_pos, void* stream);
+/* Row-compact SH adjoint: gs_sh_bwd's dense single pass for the v visible rows only.  indexes (v) int64, distinct
+ * (gs_project_fwd's list); grad_out / fwd_out are read at row i (striding and the clamp-mask shortcut as in gs_sh_bwd);
+ * d_params (v,C,D) and the optional d_positions (v,3) receive ROW i = what gs_sh_bwd writes to row indexes[i], bit for
+ * bit; nothing is written for the culled Gaussians.  d_camera_pos (3, optional) is zeroed inside, then summed. */
+int gs_sh_bwd_rows(int64_t n, int64_t v, int32_t channels, int32_t degree, const float* params, const float* positions,
+                   const int64_t* indexes, const float* camera_pos, const float* grad_out, int32_t grad_out_stride,
+                   const float* fwd_out, int32_t fwd_out_stride, float* d_params, float* d_positions,
+                   float* d_camera_pos, void* stream);
 
 /* --------------------------------------------------------------- tile mapper (a5 - a10) --
  * Fused path (what map_to_tiles runs).  replaces mapper/tile_mapper.py:169-196 as a whole:
@@ -349,6 +373,10 @@ int gs_feature_gather_fwd(int64_t v, const int32_t* v_dev, int32_t channels, con
                           const int64_t* indexes, float* out, int32_t out_stride, void* stream);
 int gs_feature_gather_bwd(int64_t n, int32_t channels, const int32_t* slot_of, const float* grad_out,
                           int32_t grad_out_stride, float* d_features, void* stream);
+/* Row-compact adjoint of the gather: d_features (v, C), row i = the first C columns of gradient row i (stride
+ * grad_out_stride, <= 0 means C) -- a strided row copy; the rows belong to the Gaussians of the visible list. */
+int gs_feature_gather_bwd_rows(int64_t v, int32_t channels, const float* grad_out, int32_t grad_out_stride,
+                               float* d_features, void* stream);
 
 /* ------------------------------------------------------- depth / depth-variance epilogue --
  * replaces: renderer.py:174-180 compute_depth_variance (+ the feature slice at :213-215) for
@@ -465,6 +493,20 @@ int gs_frame_bwd_part(const GsFrame* frame, const float* position, const float* 
                       float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
                       float* d_feature, float* d_T_camera_world, float* d_projection, float* d_camera_centre,
                       void* const* stage_events, void* stream, const GsFrameBwdPart* part);
+/* gs_frame_bwd_rows: gs_frame_bwd_part with ROW-COMPACT parameter gradients (sparse visible-row gradients; no reference
+ * counterpart): d_position (v,3), d_log_scaling (v,3), d_rotation (v,4), d_alpha_logit (v,1), d_feature (v,C[,D]), row i
+ * for Gaussian indexes[i] of the frame's visible list (layout.indexes) -- the adjoints are gs_sh_bwd_rows /
+ * gs_feature_gather_bwd_rows and gs_project_bwd_rows, nothing of size n is written.  Same trailing `part` (NULL = every
+ * stage), so a caller may run RASTER / COLOURS / PROJECT in separate calls.  Refuses a sharded frame and a row
+ * sub-range (row_begin, row_end other than 0, n) with GS_ERR_UNSUPPORTED.  The camera gradients stay dense. */
+int gs_frame_bwd_rows(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
+                      const float* alpha_logit, const float* feature, const float* T_camera_world,
+                      const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                      int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image, const float* grad_img_depth,
+                      const float* grad_img_var, const float* attached_points, const float* attached_depth,
+                      float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
+                      float* d_feature, float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                      void* const* stage_events, void* stream, const GsFrameBwdPart* part);
 
 /* ------------------------------------------------------------------- Morton ordering --
  * replaces: misc/morton_sort.py:78-88 code_points64_kernel (Grid.morton_code64, :37-66).  points (n,3);
@@ -496,6 +538,19 @@ int gs_optim_step(int32_t laprop, int32_t vector_group, int64_t rows, int32_t di
                   const float* weight, float* m, float* v, const float* total_weight, const float* grad, float lr,
                   float beta1, float beta2, float eps, int32_t bias_correction, float* lr_step,
                   const float* row_scale, float* param, const float* mask_lr, const float* point_lr, void* stream);
+/* The same step from a ROW-COMPACT gradient (the values of a frame's sparse visible-row gradient): grad (grad_count,
+ * dims); visible row i reads row grad_rows[i] of it (int32; NULL: row i, then grad_count >= rows; -1: the gradient of
+ * that row is zero, which is what a dense gradient holds for it).  Everything else as gs_optim_step, and the same
+ * arithmetic: fed the same numbers the two leave the same bits.
+ * gs_optim_grad_rows fills such a grad_rows: the position of indexes[i] in grad_indexes (grad_count int64, ASCENDING
+ * and distinct -- a frame's points_in_view), or -1; one binary search per row, no host copy, no sort. */
+int gs_optim_grad_rows(int64_t rows, const int64_t* indexes, int64_t grad_count, const int64_t* grad_indexes,
+                       int32_t* grad_rows, void* stream);
+int gs_optim_step_rows(int32_t laprop, int32_t vector_group, int64_t rows, int32_t dims, const int64_t* indexes,
+                       const float* weight, float* m, float* v, const float* total_weight, const float* grad,
+                       int64_t grad_count, const int32_t* grad_rows, float lr, float beta1, float beta2, float eps,
+                       int32_t bias_correction, float* lr_step, const float* row_scale, float* param,
+                       const float* mask_lr, const float* point_lr, void* stream);
 
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,

@@ -143,6 +143,17 @@ SIGNATURES = {
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gs_frame_bwd_part": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(GsFrameBwdPart)]),
+    # sparse visible-row gradients: row-compact adjoints, their frame call and the optimizer step that reads them
+    "gs_project_bwd_rows_scratch_bytes": (_I64, [_I64]),
+    "gs_project_bwd_rows": (ctypes.c_int, [_I64, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _CFG, _P, _P, _I32, _P, _P,
+                                            _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "gs_sh_bwd_rows": (ctypes.c_int, [_I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "gs_feature_gather_bwd_rows": (ctypes.c_int, [_I64, _I32, _P, _I32, _P, _P]),
+    "gs_frame_bwd_rows": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
+                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(GsFrameBwdPart)]),
+    "gs_optim_grad_rows": (ctypes.c_int, [_I64, _P, _I64, _P, _P, _P]),
+    "gs_optim_step_rows": (ctypes.c_int, [_I32, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, c_float, c_float,
+                                           c_float, c_float, _I32, _P, _P, _P, _P, _P, _P]),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),
@@ -228,7 +239,7 @@ class _TimedLib:
     def __getattr__(self, name):  # first lookup only: the result is stored on the instance
         fn = getattr(self._h, name)
         if name.endswith("_bytes") or name in ("gs_last_error", "gs_version", "gs_grad_row_floats", "gs_frame_layout",
-                                               "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_part",
+                                               "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_part", "gs_frame_bwd_rows",
                                                "gs_map_touched_offset", "gs_ssim_window"):
             setattr(self, name, fn)
             return fn

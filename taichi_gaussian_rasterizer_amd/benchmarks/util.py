@@ -28,6 +28,8 @@ FLAGS = {
     "alpha_threshold": dict(type=float, default=1 / 255),
     "pixel_stride": dict(type=str, default="2,2"),
     "ssim_weight": dict(type=float, default=0.2, help="weight of 1 - SSIM in the photometric loss"),
+    "scene": dict(type=str, default="both", choices=("both", "all_in_view", "quarter_in_view"),
+                  help="which of the benchmark's scenes to run (one alone: for a profiler run)"),
     "json": dict(type=str, default="", help="write the benchmark's record to this file"),
 }
 _PAIRS = ("image_size", "pixel_stride")

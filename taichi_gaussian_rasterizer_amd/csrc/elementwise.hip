@@ -62,6 +62,17 @@ __global__ __launch_bounds__(256) void feature_scatter_kernel(int64_t n, int C, 
   __builtin_nontemporal_store(slot >= 0 ? grad[int64_t(slot) * grad_stride + c] : 0.0f, d_features + e);
 }
 
+// Row-compact adjoint of the gather: row i of the (v, C) gradient is the colour columns of gradient row i -- a strided
+// row copy, one element per thread; nothing is written for the culled Gaussians.
+__global__ __launch_bounds__(256) void feature_rows_copy_kernel(int64_t v, int C, const float* grad, int grad_stride,
+                                                                float* d_features) {
+  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t i = e / C;
+  if (i >= v) return;
+  const int c = int(e - i * C);
+  __builtin_nontemporal_store(grad[i * grad_stride + c], d_features + e);
+}
+
 // Exchange buffers of a sharded frame: the rasterizer's gradient rows (V, row_floats) split into the two packed arrays
 // the ranks sum -- splat columns [0, 7 + col0) and colour columns [7 + col0, 7 + F) -- one element per thread, so both
 // sides are coalesced.  With `features` (the forward's SH colours, (V, F)) the colour gradient of a channel the forward
@@ -306,6 +317,19 @@ extern "C" int gs_feature_gather_bwd(int64_t n, int32_t channels, const int32_t*
                      static_cast<hipStream_t>(stream), n, channels, slot_of, grad_out,
                      grad_out_stride > 0 ? grad_out_stride : channels, d_features);
   GS_CHECK_LAUNCH("gs_feature_gather_bwd");
+  return GS_OK;
+}
+
+extern "C" int gs_feature_gather_bwd_rows(int64_t v, int32_t channels, const float* grad_out, int32_t grad_out_stride,
+                                          float* d_features, void* stream) {
+  GS_REQUIRE(channels >= 1, GS_ERR_INVALID_ARGUMENT, "gs_feature_gather_bwd_rows: %d channels", channels);
+  GS_REQUIRE(v >= 0, GS_ERR_INVALID_ARGUMENT, "gs_feature_gather_bwd_rows: %lld rows", (long long)v);
+  if (v == 0) return GS_OK;
+  GS_REQUIRE(grad_out && d_features, GS_ERR_INVALID_ARGUMENT, "gs_feature_gather_bwd_rows: NULL buffer");
+  hipLaunchKernelGGL(feature_rows_copy_kernel, dim3(unsigned(gs_div_up(v * channels, 256))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), v, channels, grad_out,
+                     grad_out_stride > 0 ? grad_out_stride : channels, d_features);
+  GS_CHECK_LAUNCH("gs_feature_gather_bwd_rows");
   return GS_OK;
 }
 

@@ -299,15 +299,17 @@ extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float
   return tm.rc;
 }
 
-extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const float* log_scaling,
-                                 const float* rotation, const float* alpha_logit, const float* feature,
-                                 const float* T_camera_world, const float* projection, void* workspace,
-                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
-                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
-                                 const float* attached_points, const float* attached_depth, float* d_position,
-                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
-                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
+namespace {
+
+// gs_frame_bwd_part (compact = false: (n, ...) gradients, zero rows for the culled Gaussians) and gs_frame_bwd_rows
+// (compact = true: (v, ...) gradients, row i for Gaussian indexes[i])
+int frame_bwd(bool compact, const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
+              const float* alpha_logit, const float* feature, const float* T_camera_world, const float* projection,
+              void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
+              const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+              const float* attached_points, const float* attached_depth, float* d_position, float* d_log_scaling,
+              float* d_rotation, float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
+              float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
@@ -319,6 +321,11 @@ extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const 
              "gs_frame_bwd: stages [%d, %d)", first, end);
   GS_REQUIRE(lo >= 0 && nr >= 0 && lo + nr <= d.n, GS_ERR_INVALID_ARGUMENT, "gs_frame_bwd: rows [%lld, %lld) of %lld",
              (long long)lo, (long long)(lo + nr), (long long)d.n);
+  GS_REQUIRE(!compact || !f->has_shard, GS_ERR_UNSUPPORTED,
+             "gs_frame_bwd_rows: a sharded frame has no row-compact gradients (grad_mode \"sharded\" is range-shaped)");
+  GS_REQUIRE(!compact || (lo == 0 && nr == d.n), GS_ERR_UNSUPPORTED,
+             "gs_frame_bwd_rows: a row sub-range [%lld, %lld) of %lld gaussians", (long long)lo, (long long)(lo + nr),
+             (long long)d.n);
   GS_REQUIRE(!f->has_shard || first > GS_BWD_RASTER || end <= GS_BWD_COLOURS, GS_ERR_UNSUPPORTED,
              "gs_frame_bwd: a sharded frame exchanges its partial gradients between the rasterizer and the adjoints; "
              "run [GS_BWD_RASTER, GS_BWD_COLOURS) and the later stages in separate calls");
@@ -367,7 +374,13 @@ extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const 
   }
   if (first <= GS_BWD_COLOURS && end > GS_BWD_COLOURS) {
     tm.mark(GS_BWD_COLOURS, 0, stream);
-    if (f->sh_degree >= 0)
+    if (compact && f->sh_degree >= 0)
+      rc = gs_sh_bwd_rows(d.n, v, d.C, f->sh_degree, feature, position, at<int64_t>(workspace, L.indexes),
+                          at<float>(workspace, L.camera_pos), colours, colour_stride, feats + d.col0, d.F, d_feature,
+                          nullptr, d_camera_centre, stream);
+    else if (compact)
+      rc = gs_feature_gather_bwd_rows(v, d.C, colours, colour_stride, d_feature, stream);
+    else if (f->sh_degree >= 0)
       rc = gs_sh_bwd(nr, v, d.C, f->sh_degree, feature + lo * d.C * d.D, position + 3 * lo,
                      at<int64_t>(workspace, L.indexes), 1, slot_of, at<float>(workspace, L.camera_pos), colours,
                      colour_stride, feats + d.col0, d.F, d_feature, nullptr, d_camera_centre, stream);
@@ -385,16 +398,56 @@ extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const 
     const bool camera = d_T_camera_world || d_projection;
     const float* gd = f->render_depth ? splats + 7 : (v > 0 ? attached_depth : nullptr);
     tm.mark(GS_BWD_PROJECT, 0, stream);
-    rc = gs_project_bwd(nr, v, position + 3 * lo, log_scaling + 3 * lo, rotation + 4 * lo, alpha_logit + lo,
-                        T_camera_world, projection, f->width, f->height, cfg, slot_of, splats, splat_stride, gd,
-                        f->render_depth ? splats + 8 : nullptr, f->render_depth ? splat_stride : 1, d_position,
-                        d_log_scaling, d_rotation, d_alpha_logit, d_T_camera_world, d_projection,
-                        camera ? at<char>(scratch, L.b_camera) : nullptr,
-                        camera ? gs_project_bwd_scratch_bytes(nr) : 0, stream);
+    if (compact)
+      rc = gs_project_bwd_rows(d.n, v, position, log_scaling, rotation, alpha_logit, T_camera_world, projection, f->width,
+                               f->height, cfg, at<int64_t>(workspace, L.indexes), splats, splat_stride, gd,
+                               f->render_depth ? splats + 8 : nullptr, f->render_depth ? splat_stride : 1, d_position,
+                               d_log_scaling, d_rotation, d_alpha_logit, d_T_camera_world, d_projection,
+                               camera ? at<char>(scratch, L.b_camera) : nullptr,
+                               camera ? gs_project_bwd_scratch_bytes(d.n) : 0, stream);
+    else
+      rc = gs_project_bwd(nr, v, position + 3 * lo, log_scaling + 3 * lo, rotation + 4 * lo, alpha_logit + lo,
+                          T_camera_world, projection, f->width, f->height, cfg, slot_of, splats, splat_stride, gd,
+                          f->render_depth ? splats + 8 : nullptr, f->render_depth ? splat_stride : 1, d_position,
+                          d_log_scaling, d_rotation, d_alpha_logit, d_T_camera_world, d_projection,
+                          camera ? at<char>(scratch, L.b_camera) : nullptr,
+                          camera ? gs_project_bwd_scratch_bytes(nr) : 0, stream);
     tm.mark(GS_BWD_PROJECT, 1, stream);
     if (rc) return rc;
   }
   return tm.rc;
+}
+
+}  // namespace
+
+extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const float* log_scaling,
+                                 const float* rotation, const float* alpha_logit, const float* feature,
+                                 const float* T_camera_world, const float* projection, void* workspace,
+                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
+                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+                                 const float* attached_points, const float* attached_depth, float* d_position,
+                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
+  return frame_bwd(false, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
+                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
+                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part);
+}
+
+extern "C" int gs_frame_bwd_rows(const GsFrame* f, const float* position, const float* log_scaling,
+                                 const float* rotation, const float* alpha_logit, const float* feature,
+                                 const float* T_camera_world, const float* projection, void* workspace,
+                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
+                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+                                 const float* attached_points, const float* attached_depth, float* d_position,
+                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
+  return frame_bwd(true, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
+                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
+                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part);
 }
 
 extern "C" int gs_frame_bwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,

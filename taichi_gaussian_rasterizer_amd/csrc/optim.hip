@@ -119,6 +119,109 @@ __global__ __launch_bounds__(256) void optim_vector_kernel(OptArgs a) {
   a.v[idx] = v;
 }
 
+// The same steps from a row-compact (R, dims) gradient: visible row i takes row grad_rows[i] of it (NULL: row i; -1: the
+// gradient is zero, which is what a dense gradient holds for such a row).  Kernels of their own, the arithmetic
+// restated line by line, so that the two above keep the code they had (profiles/sparse_grad/isa_identity.txt).
+// Bit-identity with the dense kernels therefore rests on the compiler contracting the same multiply-adds in two separate
+// bodies; only the torch.equal optimizer tests of tests/test_sparse_grad_gpu.py guard it (rerun them after a compiler
+// change).
+template <bool LAPROP>
+__global__ __launch_bounds__(256) void optim_scalar_rows_kernel(OptArgs a, const int* grad_rows) {
+  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= a.rows * a.dims) return;
+  const int64_t i = e / a.dims;
+  const int j = int(e - i * a.dims);
+  const int64_t idx = a.indexes[i];
+  const float w = a.weight[i], tw = a.total_weight[idx];
+  const int64_t at = idx * a.dims + j;
+  const int64_t r = grad_rows ? int64_t(grad_rows[i]) : i;
+  const float graw = r >= 0 ? a.grad[r * a.dims + j] : 0.0f;
+  const float g = a.row_scale ? graw * a.row_scale[i] : graw;
+  float m, v, step;
+  if (LAPROP) {
+    const float bias1 = a.bias_correction ? one_minus_pow(a.beta1, tw) : 1.0f;
+    const float bias2 = a.bias_correction ? one_minus_pow(a.beta2, tw) : 1.0f;
+    v = lerp_pow(a.beta2, w, a.v[at], g * g);
+    m = lerp_pow(a.beta1, w, a.m[at], g / fmaxf(sqrtf(v / bias2), a.eps));
+    step = m * a.lr / bias1;
+  } else {
+    const float bias = a.bias_correction ? sqrtf(one_minus_pow(a.beta2, tw)) / (one_minus_pow(a.beta1, tw)) : 1.0f;
+    m = lerp_pow(a.beta1, w, a.m[at], g);
+    v = lerp_pow(a.beta2, w, a.v[at], g * g);
+    step = m / fmaxf(sqrtf(v), a.eps) * bias * a.lr;
+  }
+  if (a.lr_step) a.lr_step[e] = step;
+  a.m[at] = m;
+  a.v[at] = v;
+  if (a.param) {
+    float upd = step * saturate_weight(w);
+    if (a.mask_lr) upd *= a.mask_lr[j];
+    if (a.point_lr) upd *= a.point_lr[idx];
+    a.param[at] -= upd;
+  }
+}
+
+template <bool LAPROP>
+__global__ __launch_bounds__(256) void optim_vector_rows_kernel(OptArgs a, const int* grad_rows) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= a.rows) return;
+  const int64_t idx = a.indexes[i];
+  const float w = a.weight[i], tw = a.total_weight[idx];
+  const float gs = a.row_scale ? a.row_scale[i] : 1.0f;
+  const int64_t r = grad_rows ? int64_t(grad_rows[i]) : i;
+  const bool absent = r < 0;  // zeros, read from nowhere
+  const float* grow = a.grad + (absent ? 0 : r) * a.dims;
+  float norm = 0.0f;
+  for (int j = 0; j < a.dims; ++j) { const float g = (absent ? 0.0f : grow[j]) * gs; norm += g * g; }
+  float apply = 0.0f;
+  if (a.param) {
+    apply = saturate_weight(w);
+    if (a.point_lr) apply *= a.point_lr[idx];
+  }
+  const float v = lerp_pow(a.beta2, w, a.v[idx], norm);
+  if (LAPROP) {
+    const float bias1 = a.bias_correction ? one_minus_pow(a.beta1, tw) : 1.0f;
+    const float bias2 = a.bias_correction ? one_minus_pow(a.beta2, tw) : 1.0f;
+    const float denom = fmaxf(sqrtf(v / bias2), a.eps);
+    for (int j = 0; j < a.dims; ++j) {
+      const float m = lerp_pow(a.beta1, w, a.m[idx * a.dims + j], (absent ? 0.0f : grow[j]) * gs / denom);
+      const float step = m * a.lr / bias1;
+      if (a.lr_step) a.lr_step[i * a.dims + j] = step;
+      a.m[idx * a.dims + j] = m;
+      if (a.param) a.param[idx * a.dims + j] -= step * apply * (a.mask_lr ? a.mask_lr[j] : 1.0f);
+    }
+  } else {
+    const float bias = a.bias_correction ? sqrtf(one_minus_pow(a.beta2, tw)) / (one_minus_pow(a.beta1, tw)) : 1.0f;
+    const float denom = fmaxf(sqrtf(v), a.eps);
+    for (int j = 0; j < a.dims; ++j) {
+      const float m = lerp_pow(a.beta1, w, a.m[idx * a.dims + j], (absent ? 0.0f : grow[j]) * gs);
+      const float step = m / denom * bias * a.lr;
+      if (a.lr_step) a.lr_step[i * a.dims + j] = step;
+      a.m[idx * a.dims + j] = m;
+      if (a.param) a.param[idx * a.dims + j] -= step * apply * (a.mask_lr ? a.mask_lr[j] : 1.0f);
+    }
+  }
+  a.v[idx] = v;
+}
+
+// Where the rows of `indexes` sit in an ASCENDING list of distinct row ids (a frame's points_in_view, the index list of
+// its row-compact gradients): out[i] = position of indexes[i] in it, or -1.  One binary search per row, after a look at
+// position i, which is where the row sits when `indexes` is the list itself (a step over the whole visible set).
+__global__ __launch_bounds__(256) void grad_rows_kernel(int64_t rows, const int64_t* indexes, int64_t count,
+                                                        const int64_t* sorted, int* out) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= rows) return;
+  const int64_t want = indexes[i];
+  if (i < count && sorted[i] == want) { out[i] = int(i); return; }
+  int64_t lo = 0, hi = count;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (sorted[mid] < want) lo = mid + 1;
+    else hi = mid;
+  }
+  out[i] = (lo < count && sorted[lo] == want) ? int(lo) : -1;
+}
+
 // Per-view pacing of the visibility-aware optimizers (optim/visibility_aware.py:24-31, :93-103) for the visible rows:
 // running visibility <- power mean (p = 4) of the view's visibility and the history; step weight = visibility /
 // running; total_weight += weight; gradient scale = grad_scale / (visibility + vis_smooth).
@@ -177,5 +280,47 @@ extern "C" int gs_optim_step(int32_t laprop, int32_t vector_group, int64_t rows,
     else hipLaunchKernelGGL(optim_scalar_kernel<false>, grid, dim3(256), 0, s, a);
   }
   GS_CHECK_LAUNCH("gs_optim_step");
+  return GS_OK;
+}
+
+extern "C" int gs_optim_grad_rows(int64_t rows, const int64_t* indexes, int64_t grad_count,
+                                  const int64_t* grad_indexes, int32_t* grad_rows, void* stream) {
+  GS_REQUIRE(rows >= 0 && grad_count >= 0 && grad_count < (int64_t(1) << 31), GS_ERR_INVALID_ARGUMENT,
+             "gs_optim_grad_rows: %lld rows, %lld gradient rows", (long long)rows, (long long)grad_count);
+  if (rows == 0) return GS_OK;
+  GS_REQUIRE(indexes && grad_rows && (grad_indexes || grad_count == 0), GS_ERR_INVALID_ARGUMENT,
+             "gs_optim_grad_rows: NULL buffer");
+  hipLaunchKernelGGL(grad_rows_kernel, dim3(unsigned(gs_div_up(rows, 256))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), rows, indexes, grad_count, grad_indexes, grad_rows);
+  GS_CHECK_LAUNCH("gs_optim_grad_rows");
+  return GS_OK;
+}
+
+extern "C" int gs_optim_step_rows(int32_t laprop, int32_t vector_group, int64_t rows, int32_t dims,
+                                  const int64_t* indexes, const float* weight, float* m, float* v,
+                                  const float* total_weight, const float* grad, int64_t grad_count,
+                                  const int32_t* grad_rows, float lr, float beta1, float beta2, float eps,
+                                  int32_t bias_correction, float* lr_step, const float* row_scale, float* param,
+                                  const float* mask_lr, const float* point_lr, void* stream) {
+  GS_REQUIRE(dims >= 1, GS_ERR_INVALID_ARGUMENT, "gs_optim_step_rows: dims %d", dims);
+  GS_REQUIRE(rows >= 0 && grad_count >= 0 && (grad_rows || grad_count >= rows), GS_ERR_INVALID_ARGUMENT,
+             "gs_optim_step_rows: %lld rows, %lld gradient rows and no grad_rows", (long long)rows,
+             (long long)grad_count);
+  if (rows == 0) return GS_OK;
+  GS_REQUIRE(indexes && weight && m && v && total_weight && (grad || grad_count == 0) && (lr_step || param),
+             GS_ERR_INVALID_ARGUMENT, "gs_optim_step_rows: NULL buffer");
+  OptArgs a{lr_step, indexes, weight, m, v, total_weight, grad, rows, dims, lr, beta1, beta2, eps, bias_correction,
+            row_scale, param, mask_lr, point_lr};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vector_group) {
+    const dim3 grid(unsigned(gs_div_up(rows, 256)));
+    if (laprop) hipLaunchKernelGGL(optim_vector_rows_kernel<true>, grid, dim3(256), 0, s, a, grad_rows);
+    else hipLaunchKernelGGL(optim_vector_rows_kernel<false>, grid, dim3(256), 0, s, a, grad_rows);
+  } else {
+    const dim3 grid(unsigned(gs_div_up(rows * dims, 256)));
+    if (laprop) hipLaunchKernelGGL(optim_scalar_rows_kernel<true>, grid, dim3(256), 0, s, a, grad_rows);
+    else hipLaunchKernelGGL(optim_scalar_rows_kernel<false>, grid, dim3(256), 0, s, a, grad_rows);
+  }
+  GS_CHECK_LAUNCH("gs_optim_step_rows");
   return GS_OK;
 }

@@ -122,130 +122,141 @@ struct BwdArgs {
   float* cam_partials;  // (num_blocks,16) or null
 };
 
+// The adjoint of one visible Gaussian: i = its row in the parameter tensors, slot = its row in the upstream gradients.
+// Shared by the dense kernel (one lane per Gaussian) and the row-compact one (one lane per visible row), so that a
+// visible row's four gradients are the same bits either way.
 template <bool CAMERA>
-__global__ __launch_bounds__(256) void project_bwd_kernel(BwdArgs a) {
-  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+__device__ __forceinline__ void project_bwd_row(const BwdArgs& a, const int64_t i, const int slot, float (&dpos)[3],
+                                                float (&dls)[3], float (&dq)[4], float& dal, float (&gcam_acc)[16]) {
+  const Cam c = load_cam(a.f.T44, a.f.proj);
+  Fwd f;
+  forward(a.f, c, i, f);
+  float g[7] = {0, 0, 0, 0, 0, 0, 0}, gz = 0.0f;
+  if (a.gpoints) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) g[k] = a.gpoints[int64_t(slot) * a.gpoints_stride + k];
+  }
+  if (a.gdepth) gz = a.gdepth[int64_t(slot) * a.gdepth_stride];
+  if (a.gdepth_sq) gz += 2.0f * f.cam[2] * a.gdepth_sq[int64_t(slot) * a.gdepth_stride];
+  // alpha = sigmoid(logit)
+  dal = g[6] * f.alpha * (1.0f - f.alpha);
+  // sigma = sqrt(lambda)
+  float gl1 = g[4] * 0.5f / f.s1, gl2 = g[5] * 0.5f / f.s2;
+  // axis = v / |v|
+  const float dotag = f.ax * g[2] + f.ay * g[3];
+  const float gvx = (g[2] - f.ax * dotag) / f.vn, gvy = (g[3] - f.ay * dotag) / f.vn;
+  float gc00 = gvx, gc01 = gvy, gc11 = 0.0f;
+  gl2 -= gvx;
+  // lambda1,2 = (tr +- sg)/2
+  float gtr = 0.5f * (gl1 + gl2);
+  const float gsg = 0.5f * (gl1 - gl2);
+  // sg = sqrt(max(gap,0)); at gap == 0 the reference's autodiff yields inf/NaN, we return 0
+  const float ggap = (f.gap > 0.0f && f.sg > 0.0f) ? gsg * 0.5f / f.sg : 0.0f;
+  gtr += 2.0f * f.tr * ggap;
+  const float gdet = -4.0f * ggap;
+  gc00 += gdet * f.c11 + gtr;
+  gc11 += gdet * f.c00 + gtr;
+  gc01 += -2.0f * f.c01 * gdet;
+  // cov = m m^T
+  float gN[2][3], gs[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float gm0 = 2.0f * gc00 * f.m[0][k] + gc01 * f.m[1][k];
+    const float gm1 = 2.0f * gc11 * f.m[1][k] + gc01 * f.m[0][k];
+    gs[k] = gm0 * f.N[0][k] + gm1 * f.N[1][k];
+    gN[0][k] = gm0 * f.s[k];
+    gN[1][k] = gm1 * f.s[k];
+    dls[k] = gs[k] * f.s[k];  // s = exp(log_scale)
+  }
+  // N = J M3
+  float gJ00 = 0, gJ02 = 0, gJ11 = 0, gJ12 = 0, gM3[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    gJ00 += gN[0][k] * f.M3[0][k];
+    gJ02 += gN[0][k] * f.M3[2][k];
+    gJ11 += gN[1][k] * f.M3[1][k];
+    gJ12 += gN[1][k] * f.M3[2][k];
+    gM3[0][k] = f.J00 * gN[0][k];
+    gM3[1][k] = f.J11 * gN[1][k];
+    gM3[2][k] = f.J02 * gN[0][k] + f.J12 * gN[1][k];
+  }
+  // M3 = Tr R :  gR = Tr^T gM3 ; gTr = gM3 R^T
+  float gR[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      gR[r][k] = c.T[0 * 4 + r] * gM3[0][k] + c.T[1 * 4 + r] * gM3[1][k] + c.T[2 * 4 + r] * gM3[2][k];
+      if (CAMERA) gcam_acc[r * 4 + k] += gM3[r][0] * f.R[k][0] + gM3[r][1] * f.R[k][1] + gM3[r][2] * f.R[k][2];
+    }
+  // R = quat_to_mat(qn)  (generic.py:407-416)
+  const float x = f.qn[0], y = f.qn[1], z = f.qn[2], w = f.qn[3];
+  float gq[4];
+  gq[0] = 2.0f * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2.0f * x * gR[1][1] - w * gR[1][2] + z * gR[2][0] +
+                  w * gR[2][1] - 2.0f * x * gR[2][2]);
+  gq[1] = 2.0f * (-2.0f * y * gR[0][0] + x * gR[0][1] + w * gR[0][2] + x * gR[1][0] + z * gR[1][2] - w * gR[2][0] +
+                  z * gR[2][1] - 2.0f * y * gR[2][2]);
+  gq[2] = 2.0f * (-2.0f * z * gR[0][0] - w * gR[0][1] + x * gR[0][2] + w * gR[1][0] - 2.0f * z * gR[1][1] +
+                  y * gR[1][2] + x * gR[2][0] + y * gR[2][1]);
+  gq[3] = 2.0f * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
+  // qn = q / |q|
+  const float dotq = f.qn[0] * gq[0] + f.qn[1] * gq[1] + f.qn[2] * gq[2] + f.qn[3] * gq[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) dq[k] = (gq[k] - f.qn[k] * dotq) / f.qlen;
+  // J and the projected mean
+  const float zc = f.cam[2], iz = 1.0f / zc;
+  float gzc = gz;
+  float gfx = gJ00 * iz, gfy = gJ11 * iz;
+  gzc += -gJ00 * c.fx * iz * iz - gJ11 * c.fy * iz * iz;
+  gzc += gJ02 * (f.tx - c.cx) * iz * iz + gJ12 * (f.ty - c.cy) * iz * iz;
+  float gcx = gJ02 * iz, gcy = gJ12 * iz;
+  const float gu = g[0] + (f.in_x ? -gJ02 * iz : 0.0f);  // clamp: zero gradient outside the margin
+  const float gv = g[1] + (f.in_y ? -gJ12 * iz : 0.0f);
+  gfx += gu * f.cam[0] * iz;
+  gfy += gv * f.cam[1] * iz;
+  gcx += gu; gcy += gv;
+  const float gcamx = gu * c.fx * iz, gcamy = gv * c.fy * iz;
+  gzc += -gu * c.fx * f.cam[0] * iz * iz - gv * c.fy * f.cam[1] * iz * iz;
+  // cam = Tr p + t
+  const float gcamv[3] = {gcamx, gcamy, gzc};
+  const float px = a.f.position[3 * i], py = a.f.position[3 * i + 1], pz = a.f.position[3 * i + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dpos[k] = c.T[0 * 4 + k] * gcamv[0] + c.T[1 * 4 + k] * gcamv[1] + c.T[2 * 4 + k] * gcamv[2];
+  if (CAMERA) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      gcam_acc[r * 4 + 0] += gcamv[r] * px;
+      gcam_acc[r * 4 + 1] += gcamv[r] * py;
+      gcam_acc[r * 4 + 2] += gcamv[r] * pz;
+      gcam_acc[r * 4 + 3] += gcamv[r];
+    }
+    gcam_acc[12] = gfx; gcam_acc[13] = gfy; gcam_acc[14] = gcx; gcam_acc[15] = gcy;
+  }
+}
+
+// One lane of the adjoint, whole: Gaussian i (if `valid`), upstream gradients in row `slot` (< 0: culled, zeros), the
+// four gradients to row `out`; then the block's camera partials.  The dense and the row-compact kernel differ only in
+// how they find (i, slot, out) -- everything that computes is this one body, under the same control flow.
+template <bool CAMERA>
+__device__ __forceinline__ void project_bwd_lane(const BwdArgs& a, const bool valid, const int64_t i, const int slot,
+                                                 const int64_t out) {
   float gcam_acc[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) gcam_acc[k] = 0.0f;
-  const int slot = i < a.f.n ? a.slot_of[i] : -1;
-  if (i < a.f.n) {
+  if (valid) {
     float dpos[3] = {0, 0, 0}, dls[3] = {0, 0, 0}, dq[4] = {0, 0, 0, 0}, dal = 0;
     if (slot >= 0) {
-      const Cam c = load_cam(a.f.T44, a.f.proj);
-      Fwd f;
-      forward(a.f, c, i, f);
-      float g[7] = {0, 0, 0, 0, 0, 0, 0}, gz = 0.0f;
-      if (a.gpoints) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) g[k] = a.gpoints[int64_t(slot) * a.gpoints_stride + k];
-      }
-      if (a.gdepth) gz = a.gdepth[int64_t(slot) * a.gdepth_stride];
-      if (a.gdepth_sq) gz += 2.0f * f.cam[2] * a.gdepth_sq[int64_t(slot) * a.gdepth_stride];
-      // alpha = sigmoid(logit)
-      dal = g[6] * f.alpha * (1.0f - f.alpha);
-      // sigma = sqrt(lambda)
-      float gl1 = g[4] * 0.5f / f.s1, gl2 = g[5] * 0.5f / f.s2;
-      // axis = v / |v|
-      const float dotag = f.ax * g[2] + f.ay * g[3];
-      const float gvx = (g[2] - f.ax * dotag) / f.vn, gvy = (g[3] - f.ay * dotag) / f.vn;
-      float gc00 = gvx, gc01 = gvy, gc11 = 0.0f;
-      gl2 -= gvx;
-      // lambda1,2 = (tr +- sg)/2
-      float gtr = 0.5f * (gl1 + gl2);
-      const float gsg = 0.5f * (gl1 - gl2);
-      // sg = sqrt(max(gap,0)); at gap == 0 the reference's autodiff yields inf/NaN, we return 0
-      const float ggap = (f.gap > 0.0f && f.sg > 0.0f) ? gsg * 0.5f / f.sg : 0.0f;
-      gtr += 2.0f * f.tr * ggap;
-      const float gdet = -4.0f * ggap;
-      gc00 += gdet * f.c11 + gtr;
-      gc11 += gdet * f.c00 + gtr;
-      gc01 += -2.0f * f.c01 * gdet;
-      // cov = m m^T
-      float gN[2][3], gs[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float gm0 = 2.0f * gc00 * f.m[0][k] + gc01 * f.m[1][k];
-        const float gm1 = 2.0f * gc11 * f.m[1][k] + gc01 * f.m[0][k];
-        gs[k] = gm0 * f.N[0][k] + gm1 * f.N[1][k];
-        gN[0][k] = gm0 * f.s[k];
-        gN[1][k] = gm1 * f.s[k];
-        dls[k] = gs[k] * f.s[k];  // s = exp(log_scale)
-      }
-      // N = J M3
-      float gJ00 = 0, gJ02 = 0, gJ11 = 0, gJ12 = 0, gM3[3][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        gJ00 += gN[0][k] * f.M3[0][k];
-        gJ02 += gN[0][k] * f.M3[2][k];
-        gJ11 += gN[1][k] * f.M3[1][k];
-        gJ12 += gN[1][k] * f.M3[2][k];
-        gM3[0][k] = f.J00 * gN[0][k];
-        gM3[1][k] = f.J11 * gN[1][k];
-        gM3[2][k] = f.J02 * gN[0][k] + f.J12 * gN[1][k];
-      }
-      // M3 = Tr R :  gR = Tr^T gM3 ; gTr = gM3 R^T
-      float gR[3][3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          gR[r][k] = c.T[0 * 4 + r] * gM3[0][k] + c.T[1 * 4 + r] * gM3[1][k] + c.T[2 * 4 + r] * gM3[2][k];
-          if (CAMERA) gcam_acc[r * 4 + k] += gM3[r][0] * f.R[k][0] + gM3[r][1] * f.R[k][1] + gM3[r][2] * f.R[k][2];
-        }
-      // R = quat_to_mat(qn)  (generic.py:407-416)
-      const float x = f.qn[0], y = f.qn[1], z = f.qn[2], w = f.qn[3];
-      float gq[4];
-      gq[0] = 2.0f * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2.0f * x * gR[1][1] - w * gR[1][2] + z * gR[2][0] +
-                      w * gR[2][1] - 2.0f * x * gR[2][2]);
-      gq[1] = 2.0f * (-2.0f * y * gR[0][0] + x * gR[0][1] + w * gR[0][2] + x * gR[1][0] + z * gR[1][2] - w * gR[2][0] +
-                      z * gR[2][1] - 2.0f * y * gR[2][2]);
-      gq[2] = 2.0f * (-2.0f * z * gR[0][0] - w * gR[0][1] + x * gR[0][2] + w * gR[1][0] - 2.0f * z * gR[1][1] +
-                      y * gR[1][2] + x * gR[2][0] + y * gR[2][1]);
-      gq[3] = 2.0f * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
-      // qn = q / |q|
-      const float dotq = f.qn[0] * gq[0] + f.qn[1] * gq[1] + f.qn[2] * gq[2] + f.qn[3] * gq[3];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dq[k] = (gq[k] - f.qn[k] * dotq) / f.qlen;
-      // J and the projected mean
-      const float zc = f.cam[2], iz = 1.0f / zc;
-      float gzc = gz;
-      float gfx = gJ00 * iz, gfy = gJ11 * iz;
-      gzc += -gJ00 * c.fx * iz * iz - gJ11 * c.fy * iz * iz;
-      gzc += gJ02 * (f.tx - c.cx) * iz * iz + gJ12 * (f.ty - c.cy) * iz * iz;
-      float gcx = gJ02 * iz, gcy = gJ12 * iz;
-      const float gu = g[0] + (f.in_x ? -gJ02 * iz : 0.0f);  // clamp: zero gradient outside the margin
-      const float gv = g[1] + (f.in_y ? -gJ12 * iz : 0.0f);
-      gfx += gu * f.cam[0] * iz;
-      gfy += gv * f.cam[1] * iz;
-      gcx += gu; gcy += gv;
-      const float gcamx = gu * c.fx * iz, gcamy = gv * c.fy * iz;
-      gzc += -gu * c.fx * f.cam[0] * iz * iz - gv * c.fy * f.cam[1] * iz * iz;
-      // cam = Tr p + t
-      const float gcamv[3] = {gcamx, gcamy, gzc};
-      const float px = a.f.position[3 * i], py = a.f.position[3 * i + 1], pz = a.f.position[3 * i + 2];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dpos[k] = c.T[0 * 4 + k] * gcamv[0] + c.T[1 * 4 + k] * gcamv[1] + c.T[2 * 4 + k] * gcamv[2];
-      if (CAMERA) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          gcam_acc[r * 4 + 0] += gcamv[r] * px;
-          gcam_acc[r * 4 + 1] += gcamv[r] * py;
-          gcam_acc[r * 4 + 2] += gcamv[r] * pz;
-          gcam_acc[r * 4 + 3] += gcamv[r];
-        }
-        gcam_acc[12] = gfx; gcam_acc[13] = gfy; gcam_acc[14] = gcx; gcam_acc[15] = gcy;
-      }
+      project_bwd_row<CAMERA>(a, i, slot, dpos, dls, dq, dal, gcam_acc);
     }
 #pragma unroll
     // gradients are written once and read by the optimizer later: keep them out of the caches the next frame's
     // gathers live in
-    for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(dpos[k], a.d_position + 3 * i + k);
+    for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(dpos[k], a.d_position + 3 * out + k);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(dls[k], a.d_log_scaling + 3 * i + k);
+    for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(dls[k], a.d_log_scaling + 3 * out + k);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(dq[k], a.d_rotation + 4 * i + k);
-    __builtin_nontemporal_store(dal, a.d_alpha_logit + i);
+    for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(dq[k], a.d_rotation + 4 * out + k);
+    __builtin_nontemporal_store(dal, a.d_alpha_logit + out);
   }
   if (CAMERA) {
     __shared__ float s_part[4][16];
@@ -259,6 +270,24 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(BwdArgs a) {
       a.cam_partials[int64_t(blockIdx.x) * 16 + threadIdx.x] =
           s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
   }
+}
+
+template <bool CAMERA>
+__global__ __launch_bounds__(256) void project_bwd_kernel(BwdArgs a) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int slot = i < a.f.n ? a.slot_of[i] : -1;
+  project_bwd_lane<CAMERA>(a, i < a.f.n, i, slot, i);
+}
+
+// Row-compact variant: one lane per VISIBLE row r (Gaussian indexes[r], the upstream gradient is row r), the four
+// gradients go to row r of (v, 3) (v, 3) (v, 4) (v, 1) arrays -- nothing is written for the culled Gaussians.  The camera
+// partials are per block of visible rows.  (A negative index, which the visible list never holds, would be a culled row:
+// the test keeps the control flow of the shared body that of the dense kernel.)
+template <bool CAMERA>
+__global__ __launch_bounds__(256) void project_bwd_rows_kernel(BwdArgs a, const int64_t* indexes, int64_t v) {
+  const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t i = r < v ? indexes[r] : -1;
+  project_bwd_lane<CAMERA>(a, r < v, i, i >= 0 ? int(r) : -1, r);
 }
 
 // deterministic final reduction of the per-block camera partials (one block, fixed order)
@@ -421,6 +450,54 @@ extern "C" int gs_project_bwd(int64_t n, int64_t v, const float* position, const
     hipLaunchKernelGGL(project_bwd_kernel<false>, dim3(nb), dim3(256), 0, s, b);
   }
   GS_CHECK_LAUNCH("gs_project_bwd");
+  return GS_OK;
+}
+
+extern "C" int64_t gs_project_bwd_rows_scratch_bytes(int64_t v) { return gs_project_bwd_scratch_bytes(v); }
+
+extern "C" int gs_project_bwd_rows(int64_t n, int64_t v, const float* position, const float* log_scaling,
+                                   const float* rotation, const float* alpha_logit, const float* T_camera_world,
+                                   const float* projection, int32_t width, int32_t height, const GsRasterConfig* cfg,
+                                   const int64_t* indexes, const float* grad_points, int32_t grad_points_stride,
+                                   const float* grad_depth, const float* grad_depth_sq, int32_t grad_depth_stride,
+                                   float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
+                                   float* d_T_camera_world, float* d_projection, void* scratch, int64_t scratch_bytes,
+                                   void* stream) {
+  BwdArgs b;
+  if (int rc = fill(b.f, n, position, log_scaling, rotation, alpha_logit, T_camera_world, projection, width, height,
+                    1.0, 2.0, cfg))
+    return rc;
+  GS_REQUIRE(v >= 0 && v <= n, GS_ERR_INVALID_ARGUMENT, "gs_project_bwd_rows: %lld visible rows of %lld gaussians",
+             (long long)v, (long long)n);
+  const bool camera = d_T_camera_world != nullptr || d_projection != nullptr;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (v == 0) {
+    // nothing is visible: the camera gradients are the empty sum
+    bool ok = true;
+    if (d_T_camera_world) ok &= hipMemsetAsync(d_T_camera_world, 0, 64, s) == hipSuccess;
+    if (d_projection) ok &= hipMemsetAsync(d_projection, 0, 16, s) == hipSuccess;
+    if (!ok) { gs_set_error("gs_project_bwd_rows: hipMemsetAsync failed"); return GS_ERR_LAUNCH; }
+    return GS_OK;
+  }
+  GS_REQUIRE(indexes && d_position && d_log_scaling && d_rotation && d_alpha_logit, GS_ERR_INVALID_ARGUMENT,
+             "gs_project_bwd_rows: NULL buffer");
+  const int nb = int(gs_div_up(v, 256));
+  GS_REQUIRE(!camera || (scratch && scratch_bytes >= int64_t(nb) * 64), GS_ERR_SCRATCH_TOO_SMALL,
+             "gs_project_bwd_rows: camera gradients need %lld bytes of scratch", (long long)(int64_t(nb) * 64));
+  b.slot_of = nullptr; b.gpoints = grad_points; b.gdepth = grad_depth; b.gdepth_sq = grad_depth_sq;
+  b.gpoints_stride = grad_points_stride > 0 ? grad_points_stride : 7;
+  b.gdepth_stride = grad_depth_stride > 0 ? grad_depth_stride : 1;
+  b.d_position = d_position; b.d_log_scaling = d_log_scaling; b.d_rotation = d_rotation;
+  b.d_alpha_logit = d_alpha_logit;
+  b.cam_partials = static_cast<float*>(scratch);
+  if (camera) {
+    hipLaunchKernelGGL(project_bwd_rows_kernel<true>, dim3(nb), dim3(256), 0, s, b, indexes, v);
+    hipLaunchKernelGGL(cam_reduce_kernel, dim3(1), dim3(256), 0, s, nb, b.cam_partials, d_T_camera_world,
+                       d_projection);
+  } else {
+    hipLaunchKernelGGL(project_bwd_rows_kernel<false>, dim3(nb), dim3(256), 0, s, b, indexes, v);
+  }
+  GS_CHECK_LAUNCH("gs_project_bwd_rows");
   return GS_OK;
 }
 

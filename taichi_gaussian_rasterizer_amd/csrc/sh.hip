@@ -341,6 +341,114 @@ __global__ __launch_bounds__(256) void sh_bwd_dense_kernel(int64_t n, int C, con
   }
 }
 
+// Row-compact variant of the dense adjoint: one lane per VISIBLE row i (idx = indexes[i]; the upstream gradient and the
+// forward's output are row i), the gradient goes to row i of a (v, C, D) array -- nothing is written for the culled
+// Gaussians.  Same arithmetic as sh_bwd_dense_kernel, so row i holds the bits the dense kernel writes to row idx.
+// STAGED (C*D = 48 floats): a wave's 64 rows are one contiguous 12-KiB piece of the output, staged in LDS and written
+// with coalesced 16-byte stores.  All stores are non-temporal: written once, read by the optimizer later.
+// The arithmetic is a second copy of the dense kernel's text, not a shared function: that the two give the same bits rests
+// on the compiler contracting the same multiply-adds in both bodies.  Nothing in the source forces it; the torch.equal
+// comparisons of tests/test_sparse_grad_gpu.py are the guard, and are what to run after a compiler change.
+template <int DEG, bool STAGED>
+__global__ __launch_bounds__(256) void sh_bwd_rows_kernel(int64_t v, int C, const float* params, const float* positions,
+                                                          const int64_t* indexes, const float* cam, const float* gout,
+                                                          int gout_stride, const float* fwd_out, int fwd_out_stride,
+                                                          float* d_params, float* d_positions, float* d_cam) {
+  constexpr int D = (DEG + 1) * (DEG + 1);
+  constexpr int TILE_STRIDE = 48 + 4;  // floats per staged row (+16 B: conflict-free, still 16-B aligned)
+  typedef float vec4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) float s_tile[STAGED ? 4 : 1][STAGED ? 64 * TILE_STRIDE : 1];
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  float gd[3] = {0, 0, 0};
+  if (i < v) {
+    const int64_t idx = indexes[i];
+    const float dx = positions[3 * idx] - cam[0], dy = positions[3 * idx + 1] - cam[1],
+                dz = positions[3 * idx + 2] - cam[2];
+    const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float x = dx / nrm, y = dy / nrm, z = dz / nrm;
+    float Y[D], w[D];
+    rsh<DEG>(x, y, z, Y);
+#pragma unroll
+    for (int d = 0; d < D; ++d) w[d] = 0.0f;
+    const bool need_dir = d_positions != nullptr || d_cam != nullptr;
+    for (int c = 0; c < C; ++c) {
+      float row[D];
+      float g = gout[i * gout_stride + c];
+      if (fwd_out != nullptr && !need_dir) {
+        // the forward's clamped output tells whether the clamp was active: the coefficients are not re-read
+        const float o = fwd_out[i * fwd_out_stride + c];
+        if (!(o > 0.0f && o < 1.0f)) g = 0.0f;
+      } else {
+        load_row<D>(params + (idx * C + c) * D, row);
+        float acc = 0.0f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) acc += Y[d] * row[d];
+        const float pre = acc + 0.5f;
+        if (!(pre >= 0.0f && pre <= 1.0f)) g = 0.0f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) w[d] += g * row[d];
+      }
+      if (STAGED) {
+        float* trow = s_tile[threadIdx.x >> 6] + (threadIdx.x & 63) * TILE_STRIDE + c * D;
+#pragma unroll
+        for (int d = 0; d < D; ++d) trow[d] = g * Y[d];
+      } else {
+        float* drow = d_params + (i * C + c) * D;
+        if ((D & 3) == 0) {
+          vec4* d4 = reinterpret_cast<vec4*>(drow);
+#pragma unroll
+          for (int k = 0; k < D / 4; ++k) {
+            const vec4 val = {g * Y[4 * k], g * Y[4 * k + 1], g * Y[4 * k + 2], g * Y[4 * k + 3]};
+            __builtin_nontemporal_store(val, d4 + k);
+          }
+        } else {
+#pragma unroll
+          for (int d = 0; d < D; ++d) __builtin_nontemporal_store(g * Y[d], drow + d);
+        }
+      }
+    }
+    if (DEG >= 1 && (d_positions || d_cam)) {
+      float gdir[3];
+      rsh_grad<DEG>(x, y, z, w, gdir);
+      const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
+      gd[0] = (gdir[0] - x * dot) / nrm;
+      gd[1] = (gdir[1] - y * dot) / nrm;
+      gd[2] = (gdir[2] - z * dot) / nrm;
+    }
+    if (d_positions) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(gd[k], d_positions + 3 * i + k);
+    }
+  }
+  if (STAGED) {
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row0 = int64_t(blockIdx.x) * 256 + wave * 64;  // first visible row of this wave
+    const int64_t rows = v - row0 < 64 ? v - row0 : 64;          // <= 0 for a wave past the end
+    vec4* dst = reinterpret_cast<vec4*>(d_params + row0 * 48);
+    for (int k = 0; k < 12; ++k) {
+      const int e = k * 64 + lane;  // float4 index inside the 64 x 12 tile
+      const int r = e / 12, q = e - r * 12;
+      if (r < rows) {
+        const vec4 val = *reinterpret_cast<const vec4*>(s_tile[wave] + r * TILE_STRIDE + q * 4);
+        __builtin_nontemporal_store(val, dst + e);
+      }
+    }
+  }
+  if (d_cam && DEG >= 1) {
+    __shared__ float s_part[4][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float tot = gs_wave_sum_to_lane63(gd[k]);
+      if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6][k] = tot;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3)
+      atomicAdd(d_cam + threadIdx.x,
+                -(s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x]));
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -474,5 +582,43 @@ extern "C" int gs_sh_bwd(int64_t n, int64_t v, int32_t channels, int32_t degree,
     }
   }
   GS_CHECK_LAUNCH("gs_sh_bwd");
+  return GS_OK;
+}
+
+extern "C" int gs_sh_bwd_rows(int64_t n, int64_t v, int32_t channels, int32_t degree, const float* params,
+                              const float* positions, const int64_t* indexes, const float* camera_pos,
+                              const float* grad_out, int32_t grad_out_stride, const float* fwd_out,
+                              int32_t fwd_out_stride, float* d_params, float* d_positions, float* d_camera_pos,
+                              void* stream) {
+  GS_REQUIRE(degree >= 0 && degree <= 3, GS_ERR_UNSUPPORTED, "gs_sh_bwd_rows: SH degree %d not in [0,3]", degree);
+  GS_REQUIRE(channels >= 1 && channels <= GS_MAX_SH_CHANNELS, GS_ERR_UNSUPPORTED, "gs_sh_bwd_rows: %d channels",
+             channels);
+  GS_REQUIRE(v >= 0 && v <= n, GS_ERR_INVALID_ARGUMENT, "gs_sh_bwd_rows: %lld visible rows of %lld gaussians",
+             (long long)v, (long long)n);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d_camera_pos && hipMemsetAsync(d_camera_pos, 0, 12, s) != hipSuccess) {
+    gs_set_error("gs_sh_bwd_rows: hipMemsetAsync failed");
+    return GS_ERR_LAUNCH;
+  }
+  if (v == 0) return GS_OK;
+  GS_REQUIRE(params && positions && indexes && camera_pos && grad_out && d_params, GS_ERR_INVALID_ARGUMENT,
+             "gs_sh_bwd_rows: NULL buffer");
+  if (grad_out_stride <= 0) grad_out_stride = channels;
+  if (fwd_out_stride <= 0) fwd_out_stride = channels;
+  const dim3 grid(unsigned(gs_div_up(v, 256))), block(256);
+#define SH_ROWS(DEG, STAGED)                                                                                          \
+  hipLaunchKernelGGL((sh_bwd_rows_kernel<DEG, STAGED>), grid, block, 0, s, v, channels, params, positions, indexes,   \
+                     camera_pos, grad_out, grad_out_stride, fwd_out, fwd_out_stride, d_params, d_positions, d_camera_pos)
+  if (degree == 3 && channels == 3) {
+    SH_ROWS(3, true);
+  } else {
+    switch (degree) {
+      case 0: SH_ROWS(0, false); break;
+      case 1: SH_ROWS(1, false); break;
+      case 2: SH_ROWS(2, false); break;
+      default: SH_ROWS(3, false); break;
+    }
+  }
+  GS_CHECK_LAUNCH("gs_sh_bwd_rows");
   return GS_OK;
 }

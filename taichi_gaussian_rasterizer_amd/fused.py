@@ -20,6 +20,7 @@ This is SURVEY.md 8(f)-1: in the reference that glue is ~24 % of the forward+bac
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import torch
 
@@ -46,10 +47,33 @@ def _pinned_counts(dev: torch.device) -> torch.Tensor:
 _EVENTS = {}   # device index -> ring of (torch.cuda.Event, raw handle)
 _EMPTY = {}    # (device, shape) -> cached empty placeholder outputs
 _FRAMES = {}   # frame key -> (GsFrame, GsFrameLayout)
+# sparse_grad: data_ptr of the index list of a frame's sparse gradients -> (weak reference to its storage, its length).
+# The optimizers trust a list found here to be ascending and distinct (it is a copy of points_in_view).  AccumulateGrad
+# keeps the storage of a gradient it stores first, so .grad._indices() is recognised by address; whatever autograd
+# builds from several gradients has storage of its own and is not.
+_SPARSE_INDEXES = {}
 
 
 class _Overflow(Exception):
     pass
+
+
+def _register_sparse_indexes(idx: torch.Tensor) -> None:
+    for ptr in [ptr for ptr, (ref, _) in _SPARSE_INDEXES.items() if ref() is None]:
+        del _SPARSE_INDEXES[ptr]
+    if idx.numel() > 0:
+        _SPARSE_INDEXES[idx.data_ptr()] = (weakref.ref(idx.untyped_storage()), idx.numel())
+
+
+def is_frame_sparse_grad(grad: torch.Tensor) -> bool:
+    """whether a sparse gradient is the one a single backward of a sparse_grad frame produced -- its indices are then
+    ascending and distinct although autograd has dropped the is_coalesced flag.  No device work."""
+    idx = grad._indices()
+    hit = _SPARSE_INDEXES.get(idx.data_ptr()) if idx.numel() > 0 else None
+    if hit is None or idx.dim() != 2 or idx.shape[0] != 1 or hit[1] != idx.shape[1]:
+        return False
+    storage = hit[0]()  # alive: the address has not been handed to another tensor since
+    return storage is not None and storage._cdata == idx.untyped_storage()._cdata
 
 
 def _remember(key, K, max_tile):
@@ -203,7 +227,8 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
 
 def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, image_size,
              depth_range, config: RasterConfig, render_depth: bool, use_depth16: bool, render_median: bool, shard,
-             group, holder, exchange: str, grad_mode: str, owned_range, key, k_cap: int, tile_hint: int):
+             group, holder, exchange: str, grad_mode: str, owned_range, sparse_grad: bool, key, k_cap: int,
+             tile_hint: int):
     """the forward of the frame node; `needs`: which of the seven tensors get a gradient"""
     nv.require_device(position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
                       what="render_gaussians")
@@ -215,7 +240,7 @@ def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, 
     m = dict(n=n, w=int(image_size[0]), full_h=int(image_size[1]), C=feature.shape[1],
              degree=check_sh_degree(feature) if feature.dim() == 3 else -1,  # -1: plain (N, C) features, no SH
              config=config, render_depth=render_depth, group=group, shard=shard, exchange=exchange,
-             grad_mode=grad_mode, owned_range=owned_range, rank=rank)
+             grad_mode=grad_mode, owned_range=owned_range, rank=rank, sparse_grad=sparse_grad)
     outs, ws, lists = _forward_call(m, inputs, any(needs), depth_range, use_depth16, render_median, key, k_cap,
                                     tile_hint, world, rank)
     out_image, alpha, points_v, depth_v, indexes_v, vis_out, img_depth, img_var, median = outs
@@ -345,13 +370,21 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
     # range-shaped; one allocation for the five parameter gradients
     lo, hi = m["owned_range"] if m["owned_range"] is not None else (0, n)
     nr = hi - lo
+    # sparse_grad: the adjoints write one row per VISIBLE Gaussian (gs_frame_bwd_rows); nothing of size n is allocated
+    compact = m["sparse_grad"]
+    out_rows = max(V, 1) if compact else nr
     params = (position, log_scaling, rotation, alpha_logit, feature)
-    sizes = [t.numel() if nr == n else t.numel() // n * nr for t in params]
-    flat = torch.empty((sum(sizes),), dtype=torch.float32, device=dev)
-    outs, at = [], 0
-    for t, sz in zip(params, sizes):
-        outs.append(flat.as_strided(t.shape if nr == n else (nr, *t.shape[1:]), t.stride(), at))
-        at += sz
+    sizes = [t.numel() if out_rows == n else t.numel() // n * out_rows for t in params]
+    # the compact pieces start on 256-byte boundaries whatever V is: the SH adjoint writes its rows with 16-byte stores,
+    # and a wave of the optimizer step reads 256 contiguous bytes of a piece
+    starts, at = [], 0
+    for sz in sizes:
+        starts.append(at)
+        at += -(-sz // 64) * 64 if compact else sz
+    flat = torch.empty((at,), dtype=torch.float32, device=dev)
+    outs = [flat.as_strided(t.shape if out_rows == n else (out_rows, *t.shape[1:]), t.stride(), start)
+            for t, start in zip(params, starts)]
+    frame_bwd = lib.gs_frame_bwd_rows if compact else lib.gs_frame_bwd_part
     d_T = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_T else None
     d_proj = torch.empty((4,), dtype=torch.float32, device=dev) if need_proj else None
     d_centre = None
@@ -364,11 +397,11 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
             stages.start, stages.stop, None if colours is None else colours.data_ptr(),
             None if splats is None else splats.data_ptr(), 0 if colours is None else colours.stride(0),
             0 if splats is None else splats.stride(0), lo, hi))
-        nv.check(lib.gs_frame_bwd_part(ctypes.byref(frame), *map(nv.ptr, inputs), nv.ptr(ws), L.workspace_bytes,
-                                       nv.ptr(scratch), L.bwd_scratch_bytes, V, K, nv.ptr(gi), nv.ptr(gd_), nv.ptr(gv_),
-                                       nv.ptr(att_p), nv.ptr(att_d), *map(nv.ptr, outs), nv.ptr(d_T), nv.ptr(d_proj),
-                                       nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), nv.stream(),
-                                       part), "gs_frame_bwd_part")
+        nv.check(frame_bwd(ctypes.byref(frame), *map(nv.ptr, inputs), nv.ptr(ws), L.workspace_bytes,
+                           nv.ptr(scratch), L.bwd_scratch_bytes, V, K, nv.ptr(gi), nv.ptr(gd_), nv.ptr(gv_),
+                           nv.ptr(att_p), nv.ptr(att_d), *map(nv.ptr, outs), nv.ptr(d_T), nv.ptr(d_proj),
+                           nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), nv.stream(), part),
+                 "gs_frame_bwd_rows" if compact else "gs_frame_bwd_part")
 
     call(None if whole else range(nv.GS_BWD_RASTER, nv.GS_BWD_COLOURS))
     if m["config"].compute_point_heuristic and V > 0:
@@ -385,7 +418,17 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
             wait.wait()
         _publish(ctx, rows if pp is None else pp, V)  # before the PROJECT call adds the attached gradient
         call(range(nv.GS_BWD_PROJECT, nv.GS_BWD_STAGES), splats=pp)
+    if compact:
+        outs = _as_sparse(outs, params, ws, L, V)
     return (*outs, _add_centre_grad(d_T, d_centre, T), d_proj)
+
+
+def _as_sparse(rows, params, ws, L, V):
+    """the five row-compact gradients as hybrid COO tensors over one fresh copy of points_in_view (a copy, so that
+    .grad does not keep the frame's workspace alive)"""
+    idx = _carve(ws.view(torch.int64), L.indexes, (V,)).clone().view(1, V)
+    _register_sparse_indexes(idx)
+    return [torch.sparse_coo_tensor(idx, r[:V], t.shape, is_coalesced=True) for r, t in zip(rows, params)]
 
 
 class _FrameRender(torch.autograd.Function):
@@ -444,10 +487,11 @@ def _capacity(hint):
 
 def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: bool, use_depth16: bool,
                  shard=None, group=None, render_median_depth: bool = False, exchange: str = "dense",
-                 grad_mode: str = "replicated", owned=None, owned_range=None):
+                 grad_mode: str = "replicated", owned=None, owned_range=None, sparse_grad: bool = False):
     """shard (parallel.RowShard): render only the tile rows this rank owns; the images then hold those pixel rows,
     everything per-Gaussian (`gaussians2d` included) stays in full-image coordinates.
-    See parallel.render_gaussians_sharded."""
+    See parallel.render_gaussians_sharded.
+    sparse_grad: the five Gaussian parameters receive sparse COO gradients over points_in_view (renderer.py)."""
     import weakref
 
     from .renderer import Rendering
@@ -455,7 +499,7 @@ def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: b
     args = (gaussians.position.contiguous(), gaussians.log_scaling.contiguous(), gaussians.rotation.contiguous(),
             gaussians.alpha_logit.contiguous(), gaussians.feature.contiguous(), camera_params.T_camera_world,
             camera_params.projection, camera_params.image_size, camera_params.depth_range, config, render_depth,
-            use_depth16, render_median_depth, shard, group, holder, exchange, grad_mode, owned_range)
+            use_depth16, render_median_depth, shard, group, holder, exchange, grad_mode, owned_range, bool(sparse_grad))
     size = camera_params.image_size
     key = (args[0].shape[0], int(size[0]), int(size[1]), shard, config.tile_size, bool(use_depth16))
     if owned is not None:

@@ -11,6 +11,13 @@ optim/fractional_laprop.py, optim/util.py): parameter groups hold ONE (N, ...) t
 
 with optional `mask_lr` (per column) and `point_lr` (per row) multipliers.  The moment update -- and for the
 first two group types the parameter update itself -- is one launch of gs_optim_step per group.
+
+A parameter's `.grad` may be a `torch.sparse_coo` tensor over rows, as `render_gaussians(sparse_grad=True)` leaves
+it: the step then reads the compact (V, D) values in place (gs_optim_step_rows); a row of `indexes` the gradient does
+not list takes a zero gradient, as it would from the dense tensor.  A gradient that is one backward of one frame is
+recognised by the address of its index list (fused.is_frame_sparse_grad) and trusted to be ascending: `indexes` is
+matched against it by one binary-search launch, no host copy, no sort.  Any other sparse gradient -- summed over several
+backward passes, built by hand, zero_grad(set_to_none=False) -- goes through `coalesce()` first: correct, but slower.
 """
 from __future__ import annotations
 
@@ -42,7 +49,11 @@ class _Rows:
             raise ValueError(f"unknown group type {self.kind}")
         self.num_points = tensor.shape[0]
         self.param = tensor.view(self.num_points, -1)
-        self.grad = None if tensor.grad is None else tensor.grad.view(self.num_points, -1)
+        grad = tensor.grad
+        if grad is not None and grad.is_sparse:
+            self.grad = _SparseRows(grad, self.param.shape[1])
+        else:
+            self.grad = None if grad is None else grad.view(self.num_points, -1)
 
     @property
     def per_row_moment(self) -> bool:
@@ -69,8 +80,51 @@ class _Rows:
         return self.state[key]
 
 
-def _launch(rows: _Rows, algorithm: int, indexes, weight, total_weight, grad, row_scale, in_place: bool):
-    """gs_optim_step for one group; returns lr_step (rows, D) unless the update was applied in place"""
+class _SparseRows:
+    """A sparse row gradient seen as an ascending list of distinct rows (R) and their values (R, D)."""
+
+    def __init__(self, grad: torch.Tensor, width: int):
+        from ..fused import is_frame_sparse_grad
+        if grad.sparse_dim() != 1:
+            raise ValueError(f"a sparse gradient must be sparse over rows only, got sparse_dim {grad.sparse_dim()}")
+        if not (grad.is_coalesced() or is_frame_sparse_grad(grad)):
+            grad = grad.coalesce()  # the slow path: sorts, and sums repeated rows
+        self.indexes = grad._indices()[0]
+        self.values = grad._values().reshape(self.indexes.shape[0], width)
+        if not self.values.is_contiguous():
+            self.values = self.values.contiguous()
+
+    def rows_of(self, indexes: torch.Tensor, cache: Optional[dict]):
+        """int32 (len(indexes)): the row of `values` that holds the gradient of indexes[i], -1 for none; None when
+        `indexes` IS the gradient's index list (row i)"""
+        count = self.indexes.shape[0]
+        if indexes.shape[0] == count and count > 0 and indexes.data_ptr() == self.indexes.data_ptr():
+            return None
+        key = (indexes.data_ptr(), indexes.shape[0], self.indexes.data_ptr(), count)
+        found = None if cache is None else cache.get(key)
+        if found is None:
+            nv.require_device(indexes, self.indexes, dtype=torch.int64, what="optimizer step indexes")
+            found = torch.empty((indexes.shape[0],), dtype=torch.int32, device=indexes.device)
+            nv.check(nv.lib().gs_optim_grad_rows(indexes.shape[0], nv.ptr(indexes), count, nv.ptr(self.indexes),
+                                                 nv.ptr(found), nv.stream()), "gs_optim_grad_rows")
+            if cache is not None:
+                cache[key] = found
+        return found
+
+    def gather(self, grad_rows: Optional[torch.Tensor], count: int) -> torch.Tensor:
+        """(count, D) gradient rows in the order of `indexes`, zeros where the gradient has none"""
+        if grad_rows is None:
+            return self.values
+        if self.values.shape[0] == 0:
+            return self.values.new_zeros((count, self.values.shape[1]))
+        at = grad_rows.to(torch.int64)
+        return self.values[at.clamp_min(0)] * (at >= 0).unsqueeze(1)
+
+
+def _launch(rows: _Rows, algorithm: int, indexes, weight, total_weight, grad, row_scale, in_place: bool,
+            grad_rows=None, compact: bool = False):
+    """gs_optim_step for one group; returns lr_step (rows, D) unless the update was applied in place.
+    compact: `grad` is (R, D), visible row i reads its row grad_rows[i] (gs_optim_step_rows)"""
     m, v = rows.moments()
     opt = rows.options
     grad, indexes, weight = grad.contiguous(), indexes.contiguous(), weight.contiguous()
@@ -96,6 +150,17 @@ def _launch(rows: _Rows, algorithm: int, indexes, weight, total_weight, grad, ro
         nv.require_device(rows.param, mask, per_point, what="optimizer step")
     lr_step = None if in_place else rows.param.new_zeros(count, width)
     beta1, beta2 = opt["betas"]
+    if compact:
+        nv.require_device(grad_rows, dtype=torch.int32, what="optimizer step gradient rows")
+        if grad.shape[0] > 0 and grad.shape[1] != width:
+            raise ValueError(f"{rows.name}: gradient rows have {grad.shape[1]} columns, expected {width}")
+        nv.check(nv.lib().gs_optim_step_rows(
+            algorithm, int(rows.per_row_moment), count, width, nv.ptr(indexes), nv.ptr(weight), nv.ptr(m), nv.ptr(v),
+            nv.ptr(total_weight), nv.ptr(grad) if grad.shape[0] > 0 else None, grad.shape[0], nv.ptr(grad_rows),
+            float(opt["lr"]), float(beta1), float(beta2), float(opt["eps"]), int(opt["bias_correction"]),
+            nv.ptr(lr_step), nv.ptr(scale), nv.ptr(rows.param) if in_place else None, nv.ptr(mask), nv.ptr(per_point),
+            nv.stream()), "gs_optim_step_rows")
+        return lr_step
     nv.check(nv.lib().gs_optim_step(algorithm, int(rows.per_row_moment), count, width, nv.ptr(indexes), nv.ptr(weight),
                                     nv.ptr(m), nv.ptr(v), nv.ptr(total_weight), nv.ptr(grad), float(opt["lr"]),
                                     float(beta1), float(beta2), float(opt["eps"]), int(opt["bias_correction"]),
@@ -105,9 +170,33 @@ def _launch(rows: _Rows, algorithm: int, indexes, weight, total_weight, grad, ro
 
 
 def update_rows(rows: _Rows, algorithm: int, indexes: torch.Tensor, weight: torch.Tensor, total_weight: torch.Tensor,
-                basis: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None) -> None:
-    """One fractional step of the visible rows of one group (reference optim/fractional.py:107-147 + :57-63)."""
+                basis: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None,
+                cache: Optional[dict] = None) -> None:
+    """One fractional step of the visible rows of one group (reference optim/fractional.py:107-147 + :57-63).
+    `cache`: shared by the groups of one step, so that `indexes` is matched against a sparse gradient's rows once."""
     grad = rows.grad
+    sparse = isinstance(grad, _SparseRows)
+    extra = {}
+    if sparse:
+        indexes = indexes.contiguous()
+        extra = dict(grad_rows=grad.rows_of(indexes, cache), compact=True)
+    if rows.kind == "local_vector" and sparse:
+        assert basis is not None, "basis is required for local_vector optimizer"
+        # as below, on the compact rows: the local-frame gradient of the visible rows is (len(indexes), D) already
+        visible = grad.gather(extra["grad_rows"], indexes.shape[0])
+        if row_scale is not None:
+            visible = visible * row_scale.unsqueeze(1)
+        local = torch.einsum("bij,bj->bi", torch.linalg.inv(basis), visible)
+        step = _launch(rows, algorithm, indexes, weight, total_weight, local, None, in_place=False, compact=True)
+        step = torch.einsum("bij,bj->bi", basis, step)
+        if rows.options["mask_lr"] is not None:
+            step = step * rows.options["mask_lr"].reshape(1, -1)
+        if rows.options["point_lr"] is not None:
+            step = step * rows.options["point_lr"][indexes].unsqueeze(1)
+        rows.param[indexes] -= step * saturate(weight).unsqueeze(1)
+        return
+    if sparse:
+        grad = grad.values
     if rows.kind == "local_vector":
         assert basis is not None, "basis is required for local_vector optimizer"
         # gradient into the local frame, step back out of it; the kernel sees a scratch copy of the visible rows so
@@ -123,9 +212,9 @@ def update_rows(rows: _Rows, algorithm: int, indexes: torch.Tensor, weight: torc
             step = step * rows.options["point_lr"][indexes].unsqueeze(1)
         rows.param[indexes] -= step * saturate(weight).unsqueeze(1)
     elif rows.param.is_contiguous():
-        _launch(rows, algorithm, indexes, weight, total_weight, grad, row_scale, in_place=True)
+        _launch(rows, algorithm, indexes, weight, total_weight, grad, row_scale, in_place=True, **extra)
     else:  # a parameter that is a strided view: let torch do the scatter
-        step = _launch(rows, algorithm, indexes, weight, total_weight, grad, row_scale, in_place=False)
+        step = _launch(rows, algorithm, indexes, weight, total_weight, grad, row_scale, in_place=False, **extra)
         if rows.options["mask_lr"] is not None:
             step = step * rows.options["mask_lr"].reshape(1, -1)
         if rows.options["point_lr"] is not None:
@@ -162,9 +251,10 @@ class FractionalOpt(torch.optim.Optimizer):
         total_weight = views[0].shared("total_weight")
         if not counted:
             total_weight[indexes] += weight
+        cache = {}
         for view in views:
             if view.grad is not None:
-                update_rows(view, self.algorithm, indexes, weight, total_weight, basis, row_scale)
+                update_rows(view, self.algorithm, indexes, weight, total_weight, basis, row_scale, cache)
 
     def step(self, indexes: torch.Tensor, weight: torch.Tensor, basis: Optional[torch.Tensor] = None):
         self._take_step(indexes, weight, basis)

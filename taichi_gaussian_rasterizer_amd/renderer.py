@@ -158,18 +158,35 @@ def _refuse_float64(gaussians, camera_params) -> None:
 
 def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config: RasterConfig = RasterConfig(),
                      use_sh: bool = False, render_depth: bool = False, use_depth16: bool = False,
-                     render_median_depth: bool = False) -> Rendering:
+                     render_median_depth: bool = False, sparse_grad: bool = False) -> Rendering:
     """Render one view.  `gaussians.feature` holds (N, C) features, or (N, 3, (D+1)^2) SH coefficients with
     use_sh=True.  render_depth adds depth and depth variance images, render_median_depth a second,
-    non-blended pass that picks the depth at half opacity, use_depth16 sorts on 16-bit depth codes."""
+    non-blended pass that picks the depth at half opacity, use_depth16 sorts on 16-bit depth codes.
+
+    sparse_grad (not an argument of the reference, like RasterConfig.forward_cut; pass it by keyword): the backward
+    leaves `torch.sparse_coo` gradients on position, log_scaling, rotation, alpha_logit and feature -- indices (1, V) =
+    `points_in_view` (ascending, distinct), values (V, 3) (V, 3) (V, 4) (V, 1) (V, C[, D]) -- instead of (N, ...) tensors
+    that are zero outside the view; the optimizers of `optim` step from them directly.  The camera gradients stay
+    dense.  Only frames the fused node covers (SH colours, or plain features up to 30 channels): anything else raises
+    NotImplementedError (CPU or non-float32 tensors raise the operators' device or dtype error first); an empty scene
+    (N = 0) has no rows and renders as without the switch.  Rendered values are the same either way."""
     _check_call(gaussians, camera_params, config, dict(use_sh=use_sh, render_depth=render_depth,
                                                       use_depth16=use_depth16,
-                                                      render_median_depth=render_median_depth))
+                                                      render_median_depth=render_median_depth,
+                                                      sparse_grad=sparse_grad))
     _refuse_float64(gaussians, camera_params)
     from .fused import fused_supported, render_fused
     if fused_supported(gaussians, camera_params, use_sh, render_median_depth):
         return render_fused(gaussians, camera_params, config, render_depth, use_depth16,
-                            render_median_depth=render_median_depth)
+                            render_median_depth=render_median_depth, sparse_grad=sparse_grad)
+    feature = gaussians.feature
+    if sparse_grad and gaussians.position.shape[0] > 0:
+        # an empty scene has no rows to be sparse over and renders as it always did; tensors that are not float32 on
+        # the device are refused here with the error every operator gives them
+        nv.require_device(*gaussians.shape_tensors(), feature, what="render_gaussians(sparse_grad=True)")
+        raise NotImplementedError(
+            f"render_gaussians(sparse_grad=True): only the fused frame produces sparse gradients (SH colours, or plain "
+            f"features up to 30 channels); got features of shape {tuple(feature.shape)} with use_sh={use_sh}")
 
     splats, depths, visible, sort_depths = project_with_ndc(
         *gaussians.shape_tensors(), camera_params.T_camera_world, camera_params.projection,

@@ -21,6 +21,8 @@ def count_nonfinite(t, name: str, warn: bool = False) -> dict:
         if isinstance(value, torch.Tensor):
             for label, tensor in ((path, value), (f"{path}.grad", value.grad)):
                 if tensor is not None:
+                    if tensor.is_sparse:  # a row-sparse .grad (render_gaussians(sparse_grad=True)): its stored rows
+                        tensor = tensor._values()
                     bad = int((~torch.isfinite(tensor)).sum())
                     if bad:
                         found[label] = bad
