@@ -348,6 +348,30 @@ int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const fl
 int gs_raster_bwd_unpack(int64_t v, int32_t num_features, const float* grad_rows, float* grad_points,
                          float* grad_features, float* point_heuristic, void* stream);
 
+/* Background colour and differentiable weight image (no reference counterpart: the reference composites in torch and
+ * marks the weight non-differentiable).  With T = 1 - alpha the transmittance a pixel's walk ended with:
+ *   forward:  image_c = sum_i w_i f_ic + T * background[c - background_offset]  for c >= background_offset, composited in
+ *             the kernel's epilogue; channels below background_offset (the depth features of a depth render) composite on
+ *             0.  background (device, num_features - background_offset floats) may be NULL; alpha is unchanged.
+ *   backward: image is the forward's (composited) image; grad_weight (H,W; optional) is dL/d alpha and needs the
+ *             forward's alpha image.  Both enter through each pixel's initial remaining colour only,
+ *             R0 = sum_c image_c g_c - T grad_weight, because dT/d alpha_i = -T / (1 - alpha_i); the heuristics follow
+ *             from the corrected dL/d alpha.  dL/d background_c = sum_pixels g_c T is left to the caller.
+ * A background with cfg->use_alpha_blending = 0 returns GS_ERR_UNSUPPORTED, a background_offset outside [0, F) or a
+ * grad_weight without alpha GS_ERR_INVALID_ARGUMENT, before any launch.  gs_raster_fwd / gs_raster_bwd (and the _wide
+ * and _f64 pairs below) are these calls with NULLs.
+ */
+int gs_raster_fwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                     int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order, const int32_t* heavy_tiles,
+                     float* image, float* alpha, float* visibility, const GsRowShard* shard, const float* background,
+                     int32_t background_offset, void* stream);
+int gs_raster_bwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                     int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order, const int32_t* heavy_tiles,
+                     const float* image, const float* grad_image, const float* alpha, const float* grad_weight,
+                     float* grad_rows, const GsRowShard* shard, void* stream);
+
 /* Wide features: the forward and backward above for 1 <= num_features <= GS_MAX_WIDE_FEATURES (features lifted from
  * 2D models), honouring every GsRasterConfig field gs_raster_fwd / gs_raster_bwd honour.  No tile order, heavy-tile
  * split or row shard.  The forward writes image (H,W,F) and alpha (H,W), and adds into visibility (V) as gs_raster_fwd.
@@ -362,6 +386,16 @@ int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, con
                        const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                        int32_t height, const GsRasterConfig* cfg, const float* image, const float* grad_image,
                        float* grad_points, float* grad_features, float* point_heuristic, void* stream);
+/* ... with a background / a gradient of the weight image: see gs_raster_fwd_bg / gs_raster_bwd_bg */
+int gs_raster_fwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                          const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                          int32_t height, const GsRasterConfig* cfg, float* image, float* alpha, float* visibility,
+                          const float* background, int32_t background_offset, void* stream);
+int gs_raster_bwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                          const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                          int32_t height, const GsRasterConfig* cfg, const float* image, const float* grad_image,
+                          const float* alpha, const float* grad_weight, float* grad_points, float* grad_features,
+                          float* point_heuristic, void* stream);
 
 /* ------------------------------------------------- plain features (render_gaussians(use_sh=False)) --
  * replaces: `features = gaussians.feature[indexes]` (renderer.py:166) and its index backward, inside the fused frame:
@@ -507,6 +541,35 @@ int gs_frame_bwd_rows(const GsFrame* frame, const float* position, const float* 
                       float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
                       float* d_feature, float* d_T_camera_world, float* d_projection, float* d_camera_centre,
                       void* const* stage_events, void* stream, const GsFrameBwdPart* part);
+/* The frame with a background colour and a differentiable weight image (gs_raster_fwd_bg / gs_raster_bwd_bg).
+ * gs_frame_fwd_bg: background (device, `channels` floats, may be NULL) is composited under the colour channels in the
+ * rasterizer's epilogue; the depth features of render_depth composite on 0, so depth and depth_var do not change, and
+ * the median-depth pass has no background.  gs_frame_bwd_part_bg / gs_frame_bwd_rows_bg: grad_weight (local_height x
+ * width, may be NULL) is dL/d alpha; it reads the workspace's alpha image and needs a grad_image (zeros will do).  The
+ * divisor of depth / depth_var keeps treating alpha as a constant.  The entry points above are these with NULLs. */
+int gs_frame_fwd_bg(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
+                    const float* alpha_logit, const float* feature, const float* T_camera_world,
+                    const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                    int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
+                    const float* background, void* stream);
+int gs_frame_bwd_part_bg(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
+                         const float* alpha_logit, const float* feature, const float* T_camera_world,
+                         const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                         int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
+                         const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
+                         const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
+                         float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
+                         float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part,
+                         const float* grad_weight);
+int gs_frame_bwd_rows_bg(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
+                         const float* alpha_logit, const float* feature, const float* T_camera_world,
+                         const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                         int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
+                         const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
+                         const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
+                         float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
+                         float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part,
+                         const float* grad_weight);
 
 /* ------------------------------------------------------------------- Morton ordering --
  * replaces: misc/morton_sort.py:78-88 code_points64_kernel (Grid.morton_code64, :37-66).  points (n,3);
@@ -616,6 +679,17 @@ int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, con
                       int32_t height, const GsRasterConfigF64* cfg, const double* image, const double* grad_image,
                       double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
                       int64_t scratch_bytes, void* stream);
+/* ... with a background / a gradient of the weight image: see gs_raster_fwd_bg / gs_raster_bwd_bg */
+int gs_raster_fwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
+                         const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                         int32_t height, const GsRasterConfigF64* cfg, double* image, double* alpha,
+                         double* visibility, const double* background, int32_t background_offset, void* scratch,
+                         int64_t scratch_bytes, void* stream);
+int gs_raster_bwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
+                         const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                         int32_t height, const GsRasterConfigF64* cfg, const double* image, const double* grad_image,
+                         const double* alpha, const double* grad_weight, double* grad_points, double* grad_features,
+                         double* point_heuristic, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* -------------------------------------------------------------------- photometric loss --
  * (1 - ssim_weight) * mean|x - y| + ssim_weight * (1 - SSIM(x, y)) on channel-last images, x = image (the render),

@@ -168,6 +168,26 @@ SIGNATURES = {
                                           _P]),
     "gs_raster_bwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P, _P,
                                           _I64, _P]),
+    # background colour and differentiable weight image: the entry points above are these with NULLs
+    "gs_raster_fwd_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _SHARD,
+                                         _P, _I32, _P]),
+    "gs_raster_bwd_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _P, _P,
+                                         _SHARD, _P]),
+    "gs_raster_fwd_wide_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _I32,
+                                              _P]),
+    "gs_raster_bwd_wide_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _P,
+                                              _P, _P]),
+    "gs_raster_fwd_f64_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _I32,
+                                             _P, _I64, _P]),
+    "gs_raster_bwd_f64_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, _I64, _P]),
+    "gs_frame_fwd_bg": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "gs_frame_bwd_part_bg": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
+                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             POINTER(GsFrameBwdPart), _P]),
+    "gs_frame_bwd_rows_bg": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
+                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             POINTER(GsFrameBwdPart), _P]),
     "gs_ssim_window": (ctypes.c_int, [_I32, _F64, POINTER(c_float)]),
     "gs_photo_loss_scratch_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "gs_photo_loss_fwd": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _F64,
@@ -240,6 +260,7 @@ class _TimedLib:
         fn = getattr(self._h, name)
         if name.endswith("_bytes") or name in ("gs_last_error", "gs_version", "gs_grad_row_floats", "gs_frame_layout",
                                                "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_part", "gs_frame_bwd_rows",
+                                               "gs_frame_fwd_bg", "gs_frame_bwd_part_bg", "gs_frame_bwd_rows_bg",
                                                "gs_map_touched_offset", "gs_ssim_window"):
             setattr(self, name, fn)
             return fn

@@ -139,14 +139,16 @@ extern "C" int gs_frame_layout(const GsFrame* f, GsFrameLayout* out) {
   return GS_OK;
 }
 
-extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
-                            const float* alpha_logit, const float* feature, const float* T_camera_world,
-                            const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                            int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
-                            void* stream) {
+extern "C" int gs_frame_fwd_bg(const GsFrame* f, const float* position, const float* log_scaling,
+                               const float* rotation, const float* alpha_logit, const float* feature,
+                               const float* T_camera_world, const float* projection, void* workspace,
+                               int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int32_t* counts_host,
+                               void* counts_event, void* const* stage_events, const float* background, void* stream) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
+  if (int rc = gs_check_background("gs_frame_fwd", f->cfg.use_alpha_blending, background != nullptr, d.col0, d.F))
+    return rc;
   GsFrameLayout L;
   if (int rc = gs_frame_layout(f, &L)) return rc;
   GS_REQUIRE(workspace && workspace_bytes >= L.workspace_bytes, GS_ERR_SCRATCH_TOO_SMALL,
@@ -275,8 +277,9 @@ extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float
     return rc;
   tm.mark(GS_FWD_MAP_FINISH, 1, stream);
   tm.mark(GS_FWD_RASTER, 0, stream);
-  if ((rc = gs_raster_fwd(d.n, d.F, points, feats, tile_ranges, o2p, f->k_capacity, f->width, f->height, &rcfg,
-                          tile_order, counts + 7, image, alpha, vis, shard, stream)))
+  // the background applies to the colour channels only: the depth features [0, col0) composite on 0
+  if ((rc = gs_raster_fwd_bg(d.n, d.F, points, feats, tile_ranges, o2p, f->k_capacity, f->width, f->height, &rcfg,
+                             tile_order, counts + 7, image, alpha, vis, shard, background, d.col0, stream)))
     return rc;
   tm.mark(GS_FWD_RASTER, 1, stream);
   if (f->render_depth &&
@@ -309,7 +312,8 @@ int frame_bwd(bool compact, const GsFrame* f, const float* position, const float
               const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
               const float* attached_points, const float* attached_depth, float* d_position, float* d_log_scaling,
               float* d_rotation, float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
-              float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
+              float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part,
+              const float* grad_weight) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
@@ -337,6 +341,10 @@ int frame_bwd(bool compact, const GsFrame* f, const float* position, const float
              "gs_frame_bwd: v = %lld, k = %lld", (long long)v, (long long)k);
   GS_REQUIRE(d_position && d_log_scaling && d_rotation && d_alpha_logit && d_feature, GS_ERR_INVALID_ARGUMENT,
              "gs_frame_bwd: NULL gradient output");
+  GS_REQUIRE(!grad_weight || f->cfg.use_alpha_blending, GS_ERR_UNSUPPORTED,
+             "gs_frame_bwd: grad_weight needs use_alpha_blending");
+  GS_REQUIRE(!grad_weight || grad_image || (f->render_depth && (grad_img_depth || grad_img_var)),
+             GS_ERR_INVALID_ARGUMENT, "gs_frame_bwd: grad_weight without a grad_image (pass zeros)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const GsRasterConfig* cfg = &f->cfg;
   const int32_t* counts = at<int32_t>(workspace, L.counts);
@@ -365,10 +373,11 @@ int frame_bwd(bool compact, const GsFrame* f, const float* position, const float
     }
     tm.mark(GS_BWD_RASTER, 0, stream);
     if (g_img && v > 0 && d.P > 0 && k > 0 &&
-        (rc = gs_raster_bwd(v, d.F, at<float>(workspace, L.points), feats, at<int32_t>(workspace, L.tile_ranges),
-                            at<int32_t>(workspace, L.overlap_to_point), k, f->width, f->height, cfg,
-                            at<int32_t>(workspace, L.tile_order), counts + 7, at<float>(workspace, L.image), g_img,
-                            rows, f->has_shard ? &f->shard : nullptr, stream)))
+        (rc = gs_raster_bwd_bg(v, d.F, at<float>(workspace, L.points), feats, at<int32_t>(workspace, L.tile_ranges),
+                               at<int32_t>(workspace, L.overlap_to_point), k, f->width, f->height, cfg,
+                               at<int32_t>(workspace, L.tile_order), counts + 7, at<float>(workspace, L.image), g_img,
+                               grad_weight ? at<float>(workspace, L.alpha) : nullptr, grad_weight, rows,
+                               f->has_shard ? &f->shard : nullptr, stream)))
       return rc;
     tm.mark(GS_BWD_RASTER, 1, stream);
   }
@@ -420,6 +429,38 @@ int frame_bwd(bool compact, const GsFrame* f, const float* position, const float
 
 }  // namespace
 
+extern "C" int gs_frame_bwd_part_bg(const GsFrame* f, const float* position, const float* log_scaling,
+                                 const float* rotation, const float* alpha_logit, const float* feature,
+                                 const float* T_camera_world, const float* projection, void* workspace,
+                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
+                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+                                 const float* attached_points, const float* attached_depth, float* d_position,
+                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part,
+                                    const float* grad_weight) {
+  return frame_bwd(false, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
+                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
+                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part, grad_weight);
+}
+
+extern "C" int gs_frame_bwd_rows_bg(const GsFrame* f, const float* position, const float* log_scaling,
+                                 const float* rotation, const float* alpha_logit, const float* feature,
+                                 const float* T_camera_world, const float* projection, void* workspace,
+                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
+                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+                                 const float* attached_points, const float* attached_depth, float* d_position,
+                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part,
+                                    const float* grad_weight) {
+  return frame_bwd(true, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
+                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
+                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part, grad_weight);
+}
+
 extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const float* log_scaling,
                                  const float* rotation, const float* alpha_logit, const float* feature,
                                  const float* T_camera_world, const float* projection, void* workspace,
@@ -429,10 +470,11 @@ extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const 
                                  float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
                                  float* d_T_camera_world, float* d_projection, float* d_camera_centre,
                                  void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
-  return frame_bwd(false, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
-                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
-                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
-                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part);
+  return gs_frame_bwd_part_bg(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
+                              workspace, workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth,
+                              grad_img_var, attached_points, attached_depth, d_position, d_log_scaling, d_rotation,
+                              d_alpha_logit, d_feature, d_T_camera_world, d_projection, d_camera_centre, stage_events,
+                              stream, part, nullptr);
 }
 
 extern "C" int gs_frame_bwd_rows(const GsFrame* f, const float* position, const float* log_scaling,
@@ -444,10 +486,21 @@ extern "C" int gs_frame_bwd_rows(const GsFrame* f, const float* position, const 
                                  float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
                                  float* d_T_camera_world, float* d_projection, float* d_camera_centre,
                                  void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
-  return frame_bwd(true, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
-                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
-                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
-                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part);
+  return gs_frame_bwd_rows_bg(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
+                              workspace, workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth,
+                              grad_img_var, attached_points, attached_depth, d_position, d_log_scaling, d_rotation,
+                              d_alpha_logit, d_feature, d_T_camera_world, d_projection, d_camera_centre, stage_events,
+                              stream, part, nullptr);
+}
+
+extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
+                            const float* alpha_logit, const float* feature, const float* T_camera_world,
+                            const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                            int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
+                            void* stream) {
+  return gs_frame_fwd_bg(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                         workspace_bytes, scratch, scratch_bytes, counts_host, counts_event, stage_events, nullptr,
+                         stream);
 }
 
 extern "C" int gs_frame_bwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,

@@ -39,6 +39,16 @@ static inline int gs_check_cfg(const GsRasterConfig* cfg) {
   return GS_OK;
 }
 
+// the optional background of the forward entry points: channels [offset, F) are composited on it
+static inline int gs_check_background(const char* what, int blend, bool has_background, int offset, int num_features) {
+  if (!has_background) return GS_OK;
+  GS_REQUIRE(blend, GS_ERR_UNSUPPORTED, "%s: a background needs use_alpha_blending (nothing is composited without it)",
+             what);
+  GS_REQUIRE(offset >= 0 && offset < num_features, GS_ERR_INVALID_ARGUMENT,
+             "%s: background_offset %d outside the %d feature channels", what, offset, num_features);
+  return GS_OK;
+}
+
 // ---- screen-tile sharding (GsRowShard, include/gsplat_hip.h): owned tile rows <-> local rows.  Plain struct
 // arithmetic, usable on host and device.  `rows` = tile rows of the full image.
 struct GsShard {

@@ -48,6 +48,11 @@ struct BwdArgs {
   float cmax, thr, inv_thr, sat;
   int aa, heur;
   GsShard sh;  // owned tile rows: tile ids are local, H is the full image height, the images hold the owned rows
+  // optional gradient of the weight image: dT/dalpha_i = -T / (1 - alpha_i) for the final transmittance T = 1 - weight,
+  // so dL/dweight enters as one more term of each pixel's INITIAL R, R0 = image . g - T g_W (image: the forward's,
+  // background included, which carries the background's own T bg . g).  Both NULL = the weight is a constant.
+  const float* alpha;
+  const float* grad_weight;
 };
 
 // pixel origin of a (local) tile in the full image, and the row of the image buffers it starts at
@@ -143,6 +148,16 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
           gpix[b][c] = a.grad_image[pix * a.F + c];
           R[b] += a.image[pix * a.F + c] * gpix[b][c];
         }
+    }
+  }
+  if (a.grad_weight != nullptr) {  // wave-uniform (a kernel argument); nothing inside the splat loop changes
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int X = x0 + (b & 1) * 8 + lx, Y = y0 + (b >> 1) * 8 + ly;
+      if (X < a.W && Y < a.H) {
+        const int64_t pix = int64_t(Y - y0 + yout0) * a.W + X;
+        R[b] = __builtin_fmaf(a.alpha[pix] - 1.0f, a.grad_weight[pix], R[b]);
+      }
     }
   }
 
@@ -563,12 +578,15 @@ __global__ void unpack_kernel(int64_t v, int F, int row_floats, const float* row
 
 extern "C" int32_t gs_grad_row_floats(int32_t num_features) { return int32_t(gs_align_up(9 + num_features, 16)); }
 
-extern "C" int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const float* features,
-                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
-                             const int32_t* heavy_tiles, const float* image, const float* grad_image,
-                             float* grad_rows, const GsRowShard* shard, void* stream) {
+extern "C" int gs_raster_bwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                                const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                                int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
+                                const int32_t* heavy_tiles, const float* image, const float* grad_image,
+                                const float* alpha, const float* grad_weight, float* grad_rows,
+                                const GsRowShard* shard, void* stream) {
   if (int rc = gs_check_cfg(cfg)) return rc;
+  GS_REQUIRE(!grad_weight || alpha, GS_ERR_INVALID_ARGUMENT,
+             "gs_raster_bwd: grad_weight without the forward's alpha image");
   GS_REQUIRE(width > 0 && height > 0, GS_ERR_INVALID_ARGUMENT, "gs_raster_bwd: image size %dx%d", width, height);
   GS_REQUIRE(num_features >= 1 && num_features <= GS_MAX_FEATURES, GS_ERR_UNSUPPORTED,
              "gs_raster_bwd: feature width %d not in [1,%d]", num_features, GS_MAX_FEATURES);
@@ -601,11 +619,21 @@ extern "C" int gs_raster_bwd(int64_t v, int32_t num_features, const float* point
   a.cmax = cfg->clamp_max_alpha; a.thr = cfg->alpha_threshold; a.sat = cfg->saturate_threshold;
   a.inv_thr = 1.0f / cfg->alpha_threshold;
   a.aa = cfg->antialias; a.heur = cfg->compute_point_heuristic;
+  a.alpha = alpha; a.grad_weight = grad_weight;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int mode = a.aa ? 2 : a.heur ? 1 : 0;
   if (nb == 1) return mode == 2 ? launch_fp<1, 2>(a, s) : mode == 1 ? launch_fp<1, 1>(a, s) : launch_fp<1, 0>(a, s);
   if (nb == 2) return mode == 2 ? launch_fp<2, 2>(a, s) : mode == 1 ? launch_fp<2, 1>(a, s) : launch_fp<2, 0>(a, s);
   return mode == 2 ? launch_fp<4, 2>(a, s) : mode == 1 ? launch_fp<4, 1>(a, s) : launch_fp<4, 0>(a, s);
+}
+
+extern "C" int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const float* features,
+                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
+                             const int32_t* heavy_tiles, const float* image, const float* grad_image,
+                             float* grad_rows, const GsRowShard* shard, void* stream) {
+  return gs_raster_bwd_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
+                          tile_order, heavy_tiles, image, grad_image, nullptr, nullptr, grad_rows, shard, stream);
 }
 
 extern "C" int gs_raster_bwd_unpack(int64_t v, int32_t num_features, const float* grad_rows, float* grad_points,

@@ -120,6 +120,12 @@ struct TileArgs {
   const int32_t* ranges;
   const int32_t* o2p;
   Cfg c;
+  // optional (raster_fwd.hip / raster_bwd.hip): the forward's background of channels [bg_off, F); the backward's alpha
+  // image and gradient of the weight image
+  const double* bg;
+  const double* alpha_in;
+  const double* grad_weight;
+  int bg_off;
 };
 
 // the tile's list [start, end), clamped to [0, k)
@@ -193,6 +199,11 @@ __global__ __launch_bounds__(TS * TS) void raster_fwd_f64_kernel(TileArgs a, dou
   }
   if (inside) {
     double* out = image + (int64_t(py) * a.width + px) * a.F;
+    if (a.bg != nullptr) {  // composite on the background with the final transmittance
+#pragma unroll
+      for (int ch = 0; ch < FM; ++ch)
+        if (ch >= a.bg_off && ch < a.F) acc[ch] += (1.0 - total) * a.bg[ch - a.bg_off];
+    }
 #pragma unroll
     for (int ch = 0; ch < FM; ++ch)
       if (ch < a.F) out[ch] = acc[ch];
@@ -223,6 +234,10 @@ __global__ __launch_bounds__(TS * TS) void raster_bwd_f64_kernel(TileArgs a, con
   double rem[FM];
 #pragma unroll
   for (int ch = 0; ch < FM; ++ch) rem[ch] = (inside && ch < F) ? image[pix * F + ch] : 0.0;
+  // the weight image's gradient: the background acts as a last splat of opacity 1, and the weight as one more channel
+  // whose "background" is -1 (weight = 1 - T): its remaining colour is -T g_W from the first splat to the last
+  const bool weight_grad = a.grad_weight != nullptr;
+  const double rem_w = (weight_grad && inside) ? (a.alpha_in[pix] - 1.0) * a.grad_weight[pix] : 0.0;
   double total = 0.0;
   bool done = !inside;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -254,6 +269,7 @@ __global__ __launch_bounds__(TS * TS) void raster_bwd_f64_kernel(TileArgs a, con
               const double diff = s_f[j][ch] * Ti - rem[ch] / (1.0 - al);  // :180
               alpha_grad += diff * gpix[ch];
             }
+          if (weight_grad) alpha_grad -= rem_w / (1.0 - al);
         }
       }
       const double aag = s_g[j][6] * alpha_grad;  // :184
@@ -361,6 +377,8 @@ TileArgs tile_args(int64_t v, int32_t F, const double* points, const double* fea
   a.c.cmax = cfg->clamp_max_alpha;
   a.c.thr = cfg->alpha_threshold;
   a.c.sat = forward ? 1.0 - cfg->saturate_threshold : cfg->saturate_threshold;
+  a.bg = a.alpha_in = a.grad_weight = nullptr;
+  a.bg_off = 0;
   return a;
 }
 
@@ -437,20 +455,23 @@ extern "C" int64_t gs_raster_f64_scratch_bytes(int64_t v, int64_t k, int32_t num
   return records(k, num_features) + gs_f64_group_scratch_bytes(k, v, 4);
 }
 
-extern "C" int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
-                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, double* image,
-                                 double* alpha, double* visibility, void* scratch, int64_t scratch_bytes,
-                                 void* stream) {
+extern "C" int gs_raster_fwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
+                                    const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                    int32_t width, int32_t height, const GsRasterConfigF64* cfg, double* image,
+                                    double* alpha, double* visibility, const double* background,
+                                    int32_t background_offset, void* scratch, int64_t scratch_bytes, void* stream) {
   if (int rc = check_raster(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
                             image, alpha, scratch, scratch_bytes, "gs_raster_fwd_f64"))
+    return rc;
+  if (int rc = gs_check_background("gs_raster_fwd_f64", cfg->use_alpha_blending, background != nullptr,
+                                   background_offset, num_features))
     return rc;
   const bool want_vis = cfg->compute_visibility != 0;
   GS_REQUIRE(!want_vis || v == 0 || visibility, GS_ERR_INVALID_ARGUMENT,
              "gs_raster_fwd_f64: NULL visibility with compute_visibility");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const TileArgs a = tile_args(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                               true);
+  TileArgs a = tile_args(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg, true);
+  a.bg = background; a.bg_off = background ? background_offset : 0;
   const int tiles = a.tiles_x * int(gs_div_up(height, cfg->tile_size));
   double* rec = want_vis ? static_cast<double*>(scratch) : nullptr;
   if (rec && k > 0 && hipMemsetAsync(rec, 0, size_t(k) * 8, s) != hipSuccess) {  // entries in no tile's list
@@ -473,21 +494,24 @@ extern "C" int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* 
   return GS_OK;
 }
 
-extern "C" int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
-                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, const double* image,
-                                 const double* grad_image, double* grad_points, double* grad_features,
-                                 double* point_heuristic, void* scratch, int64_t scratch_bytes, void* stream) {
+extern "C" int gs_raster_bwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
+                                    const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                    int32_t width, int32_t height, const GsRasterConfigF64* cfg, const double* image,
+                                    const double* grad_image, const double* alpha, const double* grad_weight,
+                                    double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
+                                    int64_t scratch_bytes, void* stream) {
   if (int rc = check_raster(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
                             image, grad_image, scratch, scratch_bytes, "gs_raster_bwd_f64"))
     return rc;
   GS_REQUIRE(cfg->use_alpha_blending, GS_ERR_UNSUPPORTED,
              "gs_raster_bwd_f64: use_alpha_blending = false has no backward (reference backward.py blends)");
+  GS_REQUIRE(!grad_weight || alpha, GS_ERR_INVALID_ARGUMENT,
+             "gs_raster_bwd_f64: grad_weight without the forward's alpha image");
   GS_REQUIRE(v == 0 || (grad_points && grad_features && (!cfg->compute_point_heuristic || point_heuristic)),
              GS_ERR_INVALID_ARGUMENT, "gs_raster_bwd_f64: NULL gradient buffer");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const TileArgs a = tile_args(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                               false);
+  TileArgs a = tile_args(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg, false);
+  a.alpha_in = alpha; a.grad_weight = grad_weight;
   const int tiles = a.tiles_x * int(gs_div_up(height, cfg->tile_size));
   const int R = 9 + num_features;
   double* rec = static_cast<double*>(scratch);
@@ -509,4 +533,23 @@ extern "C" int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* 
                      7, grad_features, num_features, cfg->compute_point_heuristic ? point_heuristic : nullptr);
   GS_CHECK_LAUNCH("gs_raster_bwd_f64/sum");
   return GS_OK;
+}
+
+extern "C" int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
+                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, double* image,
+                                 double* alpha, double* visibility, void* scratch, int64_t scratch_bytes,
+                                 void* stream) {
+  return gs_raster_fwd_f64_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
+                              image, alpha, visibility, nullptr, 0, scratch, scratch_bytes, stream);
+}
+
+extern "C" int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
+                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, const double* image,
+                                 const double* grad_image, double* grad_points, double* grad_features,
+                                 double* point_heuristic, void* scratch, int64_t scratch_bytes, void* stream) {
+  return gs_raster_bwd_f64_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
+                              image, grad_image, nullptr, nullptr, grad_points, grad_features, point_heuristic, scratch,
+                              scratch_bytes, stream);
 }

@@ -48,6 +48,10 @@ struct FwdArgs {
   float cut;  // a region is walked while some pixel's transmittance is above this (GsRasterConfig.forward_cut)
   int blend, vis, aa;
   GsShard sh;  // owned tile rows: tile ids are local, H is the full image height, the image holds the owned rows
+  // optional background colour (device, F - bg_off floats): channels [bg_off, F) are composited on it in the epilogue,
+  // image_c = sum_i w_i f_ic + T bg_c with T the transmittance the walk ended with; NULL = composite on nothing
+  const float* bg;
+  int bg_off;
 };
 
 // pixel origin of a (local) tile in the full image, and the row of the output buffer it starts at
@@ -271,6 +275,11 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
     const int X = x0 + (b & 1) * 8 + lx, Y = y0 + (b >> 1) * 8 + ly;
     const int64_t pix = int64_t(Y - y0 + yout0) * a.W + X;
     float* out = a.image + pix * a.F;
+    if (a.bg != nullptr) {  // wave-uniform (a kernel argument): one fma per channel, only in a call with a background
+#pragma unroll
+      for (int c = 0; c < FP; ++c)
+        if (c >= a.bg_off && c < a.F) acc[b][c] = __builtin_fmaf(Tr[b], a.bg[c - a.bg_off], acc[b][c]);
+    }
 #pragma unroll
     for (int c = 0; c < FP; ++c)
       if (c < a.F) out[c] = acc[b][c];
@@ -332,12 +341,16 @@ int launch_fp(const FwdArgs& a, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* points, const float* features,
-                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
-                             const int32_t* heavy_tiles, float* image, float* alpha, float* visibility,
-                             const GsRowShard* shard, void* stream) {
+extern "C" int gs_raster_fwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                                const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                                int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
+                                const int32_t* heavy_tiles, float* image, float* alpha, float* visibility,
+                                const GsRowShard* shard, const float* background, int32_t background_offset,
+                                void* stream) {
   if (int rc = gs_check_cfg(cfg)) return rc;
+  if (int rc = gs_check_background("gs_raster_fwd", cfg->use_alpha_blending, background != nullptr, background_offset,
+                                   num_features))
+    return rc;
   GS_REQUIRE(width > 0 && height > 0, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd: image size %dx%d", width, height);
   GS_REQUIRE(num_features >= 1 && num_features <= GS_MAX_FEATURES, GS_ERR_UNSUPPORTED,
              "gs_raster_fwd: feature width %d not in [1,%d]", num_features, GS_MAX_FEATURES);
@@ -373,6 +386,7 @@ extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* point
   // stops here: forward_cut = 0 differs from the reference by < N * 2^-24 * max|feature| (N remaining splats)
   a.cut = cfg->forward_cut > 2.98023223876953125e-08f ? cfg->forward_cut : 2.98023223876953125e-08f;
   a.blend = cfg->use_alpha_blending; a.vis = vis; a.aa = cfg->antialias;
+  a.bg = background; a.bg_off = background ? background_offset : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int mode = (!a.blend && !a.aa && !a.vis) ? 3 : (!a.blend || a.aa) ? 2 : a.vis ? 1 : 0;
   if (nb == 1)
@@ -383,4 +397,13 @@ extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* point
                                                                                               : launch_fp<2, 0>(a, s);
   return mode == 3 ? launch_fp<4, 3>(a, s) : mode == 2 ? launch_fp<4, 2>(a, s) : mode == 1 ? launch_fp<4, 1>(a, s)
                                                                                             : launch_fp<4, 0>(a, s);
+}
+
+extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* points, const float* features,
+                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
+                             const int32_t* heavy_tiles, float* image, float* alpha, float* visibility,
+                             const GsRowShard* shard, void* stream) {
+  return gs_raster_fwd_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
+                          tile_order, heavy_tiles, image, alpha, visibility, shard, nullptr, 0, stream);
 }

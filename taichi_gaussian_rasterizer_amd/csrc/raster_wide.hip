@@ -39,6 +39,10 @@ struct WideArgs {
   float* grad_points;       // backward (V,7)
   float* grad_features;     // backward (V,F)
   float* heur;              // backward (V,2), optional
+  const float* bg;          // forward, optional: background of channels [bg_off, F) (raster_fwd.hip)
+  const float* alpha_in;    // backward, optional: the forward's alpha ...
+  const float* grad_weight; // ... and the gradient of the weight image (raster_bwd.hip: R0 = image . g - T g_W)
+  int bg_off;
   int W, H, F;
   int tiles_wide, tile_size, side;  // side = tile_size / 8 regions per tile row
   int num_items;
@@ -209,6 +213,24 @@ __global__ __launch_bounds__(64) void raster_fwd_wide_kernel(const WideArgs a) {
     }
   }
   if (inb) a.alpha[int64_t(Y) * a.W + X] = a.blend ? 1.0f - Tr : (Tr < 1.0f ? 1.0f : 0.0f);  // forward.py:134-137
+  if (a.bg != nullptr) {
+    // composite on the background: image_c += T bg_c with the transmittance the walk ended with, each lane for the 4
+    // pixels x 8 channels per chunk it owns in the product (the wave owns its pixels: a load-add-store as above)
+    __syncthreads();  // s_w is free: every batch ends on a barrier, and an empty list never used it
+    s_w[0][lane] = Tr;
+    __syncthreads();
+    const float4 t4 = *reinterpret_cast<const float4*>(&s_w[0][4 * pg]);
+    const float tv[4] = {t4.x, t4.y, t4.z, t4.w};
+    for (int k0 = 0; k0 < a.F; k0 += WC)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (float* o = out_at(i))
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int c = k0 + 8 * cg + j;
+            if (c < a.F && c >= a.bg_off) o[c] = __builtin_fmaf(tv[i], a.bg[c - a.bg_off], o[c]);
+          }
+  }
 }
 
 __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
@@ -249,6 +271,10 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
       R = __builtin_fmaf(u.x, g.x, __builtin_fmaf(u.y, g.y, __builtin_fmaf(u.z, g.z, __builtin_fmaf(u.w, g.w, R))));
     }
     __syncthreads();
+  }
+  if (a.grad_weight != nullptr && inb) {
+    const int64_t pix = int64_t(Y) * a.W + X;
+    R = __builtin_fmaf(a.alpha_in[pix] - 1.0f, a.grad_weight[pix], R);
   }
 
   const int2 range_v = a.ranges[tile];
@@ -482,12 +508,17 @@ int wide_setup(const char* what, int32_t num_features, int32_t width, int32_t he
 
 }  // namespace
 
-extern "C" int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
-                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                                  int32_t height, const GsRasterConfig* cfg, float* image, float* alpha,
-                                  float* visibility, void* stream) {
+extern "C" int gs_raster_fwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                     int32_t width, int32_t height, const GsRasterConfig* cfg, float* image,
+                                     float* alpha, float* visibility, const float* background,
+                                     int32_t background_offset, void* stream) {
   WideArgs a;
   if (int rc = wide_setup("gs_raster_fwd_wide", num_features, width, height, cfg, a)) return rc;
+  if (int rc = gs_check_background("gs_raster_fwd_wide", cfg->use_alpha_blending, background != nullptr,
+                                   background_offset, num_features))
+    return rc;
+  a.bg = background; a.bg_off = background ? background_offset : 0;
   GS_REQUIRE(image && alpha && tile_ranges, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd_wide: NULL output or ranges");
   GS_REQUIRE(k == 0 || (points && features && overlap_to_point), GS_ERR_INVALID_ARGUMENT,
              "gs_raster_fwd_wide: NULL input with %lld overlaps", (long long)k);
@@ -501,13 +532,16 @@ extern "C" int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* 
   return GS_OK;
 }
 
-extern "C" int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
-                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                                  int32_t height, const GsRasterConfig* cfg, const float* image,
-                                  const float* grad_image, float* grad_points, float* grad_features,
-                                  float* point_heuristic, void* stream) {
+extern "C" int gs_raster_bwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
+                                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                     int32_t width, int32_t height, const GsRasterConfig* cfg, const float* image,
+                                     const float* grad_image, const float* alpha, const float* grad_weight,
+                                     float* grad_points, float* grad_features, float* point_heuristic, void* stream) {
   WideArgs a;
   if (int rc = wide_setup("gs_raster_bwd_wide", num_features, width, height, cfg, a)) return rc;
+  GS_REQUIRE(!grad_weight || alpha, GS_ERR_INVALID_ARGUMENT,
+             "gs_raster_bwd_wide: grad_weight without the forward's alpha image");
+  a.alpha_in = alpha; a.grad_weight = grad_weight;
   GS_REQUIRE(cfg->use_alpha_blending, GS_ERR_UNSUPPORTED,
              "gs_raster_bwd_wide: no gradient is defined without alpha blending");
   GS_REQUIRE(image && grad_image && tile_ranges, GS_ERR_INVALID_ARGUMENT, "gs_raster_bwd_wide: NULL image or ranges");
@@ -522,4 +556,21 @@ extern "C" int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* 
                      static_cast<hipStream_t>(stream), a);
   GS_CHECK_LAUNCH("gs_raster_bwd_wide");
   return GS_OK;
+}
+
+extern "C" int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
+                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                                  int32_t height, const GsRasterConfig* cfg, float* image, float* alpha,
+                                  float* visibility, void* stream) {
+  return gs_raster_fwd_wide_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
+                               image, alpha, visibility, nullptr, 0, stream);
+}
+
+extern "C" int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
+                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                                  int32_t height, const GsRasterConfig* cfg, const float* image,
+                                  const float* grad_image, float* grad_points, float* grad_features,
+                                  float* point_heuristic, void* stream) {
+  return gs_raster_bwd_wide_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
+                               image, grad_image, nullptr, nullptr, grad_points, grad_features, point_heuristic, stream);
 }

@@ -177,7 +177,7 @@ def _counts_event(dev: torch.device):
 
 
 def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median, key, k_cap, tile_hint, world,
-                  rank):
+                  rank, background=None):
     """fills the frame by one gs_frame_fwd call into a workspace sized for k_cap overlaps (raises _Overflow when the
     frame has more); returns its outputs, the workspace and, for a sparse exchange, the lists gs_frame_fwd prepared"""
     position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
@@ -193,10 +193,12 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
     scratch = torch.empty((L.fwd_scratch_bytes,), dtype=torch.uint8, device=dev)
     host_counts = _pinned_counts(dev)
     ready, ready_handle = _counts_event(dev)
-    nv.check(lib.gs_frame_fwd(ctypes.byref(frame), nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation),
-                              nv.ptr(alpha_logit), nv.ptr(feature), nv.ptr(T), nv.ptr(proj), nv.ptr(ws),
-                              L.workspace_bytes, nv.ptr(scratch), L.fwd_scratch_bytes, nv.ptr(host_counts),
-                              ready_handle, nv.stage_events(nv.FRAME_FWD_STAGES), nv.stream()), "gs_frame_fwd")
+    # background None: gs_frame_fwd itself (which is this call with NULL)
+    nv.check(lib.gs_frame_fwd_bg(ctypes.byref(frame), nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation),
+                                 nv.ptr(alpha_logit), nv.ptr(feature), nv.ptr(T), nv.ptr(proj), nv.ptr(ws),
+                                 L.workspace_bytes, nv.ptr(scratch), L.fwd_scratch_bytes, nv.ptr(host_counts),
+                                 ready_handle, nv.stage_events(nv.FRAME_FWD_STAGES), nv.ptr(background), nv.stream()),
+             "gs_frame_fwd")
     ready.synchronize()  # waits for the mapper's scan only, not for the rasterizer
     host = host_counts.tolist()
     K, max_tile, overflow, V = host[0], host[1], host[2], host[4]
@@ -228,10 +230,11 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
 def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, image_size,
              depth_range, config: RasterConfig, render_depth: bool, use_depth16: bool, render_median: bool, shard,
              group, holder, exchange: str, grad_mode: str, owned_range, sparse_grad: bool, key, k_cap: int,
-             tile_hint: int):
+             tile_hint: int, background=None, differentiable_weight: bool = False):
     """the forward of the frame node; `needs`: which of the seven tensors get a gradient"""
-    nv.require_device(position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
+    nv.require_device(position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, background,
                       what="render_gaussians")
+    background = None if background is None else background.contiguous()
     inputs = (position, log_scaling, rotation, alpha_logit, feature, T_camera_world.contiguous(),
               projection.contiguous())
     dev = position.device
@@ -240,9 +243,10 @@ def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, 
     m = dict(n=n, w=int(image_size[0]), full_h=int(image_size[1]), C=feature.shape[1],
              degree=check_sh_degree(feature) if feature.dim() == 3 else -1,  # -1: plain (N, C) features, no SH
              config=config, render_depth=render_depth, group=group, shard=shard, exchange=exchange,
-             grad_mode=grad_mode, owned_range=owned_range, rank=rank, sparse_grad=sparse_grad)
+             grad_mode=grad_mode, owned_range=owned_range, rank=rank, sparse_grad=sparse_grad,
+             weight_grad=bool(differentiable_weight))
     outs, ws, lists = _forward_call(m, inputs, any(needs), depth_range, use_depth16, render_median, key, k_cap,
-                                    tile_hint, world, rank)
+                                    tile_hint, world, rank, background)
     out_image, alpha, points_v, depth_v, indexes_v, vis_out, img_depth, img_var, median = outs
 
     vis_out, img_depth, img_var, median = (_empty(dev, (0,)) if t is None else t
@@ -260,7 +264,9 @@ def _forward(ctx, needs, position, log_scaling, rotation, alpha_logit, feature, 
     # outputs nobody differentiates through (projected splats, depths) must not cost zero-filled gradients
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(*inputs, ws)
-    ctx.mark_non_differentiable(alpha, indexes_v, vis_out, heur, median)
+    ctx.mark_non_differentiable(indexes_v, vis_out, heur, median)
+    if not differentiable_weight:
+        ctx.mark_non_differentiable(alpha)
     if not render_depth:
         ctx.mark_non_differentiable(img_depth, img_var)
     return out_image, alpha, points_v, depth_v, indexes_v, vis_out, heur, img_depth, img_var, median
@@ -336,10 +342,12 @@ def _exchange(m, rows, feats):
     return pf, pp, None
 
 
-def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
+def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha=None):
     """the frame's backward on the workspace of its gs_frame_fwd: one gs_frame_bwd call when the forward prepared it,
     otherwise three -- rasterizer, colour adjoint, projection adjoint -- with a sharded frame's exchange of its partial
-    gradients after the first; returns the seven input gradients"""
+    gradients after the first; returns the seven input gradients.  g_alpha: the gradient of image_weight of a frame
+    rendered with differentiable_weight (the rasterizer's backward takes it into every pixel's initial R; the divisor
+    of depth / depth_var stays a constant)"""
     saved = ctx.saved_tensors
     inputs, ws = saved[:7], saved[7]
     position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
@@ -364,7 +372,10 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
         gv_ = g_img_var.contiguous() if g_img_var is not None else None
     att_p = g_points.contiguous() if (g_points is not None and V > 0) else None
     att_d = g_depth.contiguous() if (g_depth is not None and V > 0) else None
-    nv.require_device(gi, gd_, gv_, att_p, att_d, what="render_gaussians backward")
+    gw = g_alpha.contiguous() if (g_alpha is not None and m["weight_grad"]) else None
+    if gw is not None and gi is None and gd_ is None and gv_ is None:
+        gi = torch.zeros((L.local_height, m["w"], m["C"]), dtype=torch.float32, device=dev)  # only the weight has a gradient
+    nv.require_device(gi, gd_, gv_, att_p, att_d, gw, what="render_gaussians backward")
     need_T, need_proj = ctx.camera_grads
     # grad_mode "sharded": the adjoints run on this rank's index range [lo, hi) only and the gradients come out
     # range-shaped; one allocation for the five parameter gradients
@@ -384,7 +395,8 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
     flat = torch.empty((at,), dtype=torch.float32, device=dev)
     outs = [flat.as_strided(t.shape if out_rows == n else (out_rows, *t.shape[1:]), t.stride(), start)
             for t, start in zip(params, starts)]
-    frame_bwd = lib.gs_frame_bwd_rows if compact else lib.gs_frame_bwd_part
+    # grad_weight None: gs_frame_bwd_rows / gs_frame_bwd_part themselves (which are these calls with NULL)
+    frame_bwd = lib.gs_frame_bwd_rows_bg if compact else lib.gs_frame_bwd_part_bg
     d_T = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_T else None
     d_proj = torch.empty((4,), dtype=torch.float32, device=dev) if need_proj else None
     d_centre = None
@@ -400,7 +412,8 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var):
         nv.check(frame_bwd(ctypes.byref(frame), *map(nv.ptr, inputs), nv.ptr(ws), L.workspace_bytes,
                            nv.ptr(scratch), L.bwd_scratch_bytes, V, K, nv.ptr(gi), nv.ptr(gd_), nv.ptr(gv_),
                            nv.ptr(att_p), nv.ptr(att_d), *map(nv.ptr, outs), nv.ptr(d_T), nv.ptr(d_proj),
-                           nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), nv.stream(), part),
+                           nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), nv.stream(), part,
+                           nv.ptr(gw)),
                  "gs_frame_bwd_rows" if compact else "gs_frame_bwd_part")
 
     call(None if whole else range(nv.GS_BWD_RASTER, nv.GS_BWD_COLOURS))
@@ -431,6 +444,21 @@ def _as_sparse(rows, params, ws, L, V):
     return [torch.sparse_coo_tensor(idx, r[:V], t.shape, is_coalesced=True) for r, t in zip(rows, params)]
 
 
+_BACKGROUND_ARG = 23  # position of `background` among the arguments of _forward behind ctx and needs
+
+
+def _background_grad(ctx, g_image):
+    """dL/dbackground_c = sum over the pixels of g_c T with T = 1 - image_weight, in torch on the stream: off the default
+    path, and without a host synchronisation"""
+    m = ctx.meta
+    C = m["C"]
+    if g_image is None:
+        return torch.zeros((C,), dtype=torch.float32, device=ctx.saved_tensors[0].device)
+    L = m["frame"][1]
+    alpha = _carve(ctx.saved_tensors[7].view(torch.float32), L.alpha, (L.local_height, m["w"]))
+    return (g_image * (1.0 - alpha).unsqueeze(-1)).sum((0, 1))
+
+
 class _FrameRender(torch.autograd.Function):
     """the whole frame as one autograd node; forward arguments: see _forward"""
 
@@ -441,10 +469,13 @@ class _FrameRender(torch.autograd.Function):
 
     @staticmethod
     @nv.on_tensor_device
-    def backward(ctx, g_image, _g_alpha, g_points, g_depth, _g_idx, _g_vis, _g_heur, g_img_depth, g_img_var,
+    def backward(ctx, g_image, g_alpha, g_points, g_depth, _g_idx, _g_vis, _g_heur, g_img_depth, g_img_var,
                  _g_median=None):
-        d = _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var)
-        return d + (None,) * (len(ctx.needs_input_grad) - len(d))
+        d = _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha)
+        rest = [None] * (len(ctx.needs_input_grad) - len(d))
+        if len(rest) > _BACKGROUND_ARG - 7 and ctx.needs_input_grad[_BACKGROUND_ARG]:
+            rest[_BACKGROUND_ARG - 7] = _background_grad(ctx, g_image)
+        return d + tuple(rest)
 
 
 class _OwnedRender(torch.autograd.Function):
@@ -487,14 +518,19 @@ def _capacity(hint):
 
 def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: bool, use_depth16: bool,
                  shard=None, group=None, render_median_depth: bool = False, exchange: str = "dense",
-                 grad_mode: str = "replicated", owned=None, owned_range=None, sparse_grad: bool = False):
+                 grad_mode: str = "replicated", owned=None, owned_range=None, sparse_grad: bool = False,
+                 background=None, differentiable_weight: bool = False):
     """shard (parallel.RowShard): render only the tile rows this rank owns; the images then hold those pixel rows,
     everything per-Gaussian (`gaussians2d` included) stays in full-image coordinates.
     See parallel.render_gaussians_sharded.
-    sparse_grad: the five Gaussian parameters receive sparse COO gradients over points_in_view (renderer.py)."""
+    sparse_grad: the five Gaussian parameters receive sparse COO gradients over points_in_view (renderer.py).
+    background, differentiable_weight: see renderer.render_gaussians; not with a shard."""
     import weakref
 
     from .renderer import Rendering
+    if shard is not None and (background is not None or differentiable_weight):
+        raise NotImplementedError("render_fused: a sharded frame has neither a background nor a differentiable "
+                                  "image_weight (parallel.render_gaussians_sharded does not take the arguments)")
     holder = {}
     args = (gaussians.position.contiguous(), gaussians.log_scaling.contiguous(), gaussians.rotation.contiguous(),
             gaussians.alpha_logit.contiguous(), gaussians.feature.contiguous(), camera_params.T_camera_world,
@@ -512,7 +548,7 @@ def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: b
             return _OwnedRender.apply(*own, full, (*args[7:], key, *sizes))
     else:
         def render(*sizes):
-            return _FrameRender.apply(*args, key, *sizes)
+            return _FrameRender.apply(*args, key, *sizes, background, bool(differentiable_weight))
     # a shape seen for the first time gets the smallest capacity class
     outs = None
     try:

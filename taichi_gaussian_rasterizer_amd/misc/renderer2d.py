@@ -21,11 +21,14 @@ def project_gaussians2d(points: Gaussians2D) -> torch.Tensor:
 
 
 def render_gaussians(gaussians: Gaussians2D, image_size: Tuple[Integral, Integral],
-                     raster_config: RasterConfig = RasterConfig()):
+                     raster_config: RasterConfig = RasterConfig(), background: Optional[torch.Tensor] = None,
+                     differentiable_weight: bool = False):
+    """background (C,), differentiable_weight: see rasterizer.function.rasterize_with_tiles (not in the reference)"""
     from ..rasterizer.function import rasterize
     gaussians2d = project_gaussians2d(gaussians)
     return rasterize(gaussians2d=gaussians2d, depth=torch.clamp(gaussians.z_depth, 0, 1),
-                     features=gaussians.feature, image_size=image_size, config=raster_config)
+                     features=gaussians.feature, image_size=image_size, config=raster_config, background=background,
+                     differentiable_weight=differentiable_weight)
 
 
 def _unit_axes(points: Gaussians2D):

@@ -20,7 +20,7 @@ from .data_types import Gaussians3D, RasterConfig
 from .mapper.tile_mapper import map_to_tiles
 from .perspective.params import CameraParams
 from .perspective.projection import project_with_ndc
-from .rasterizer.function import rasterize_with_tiles
+from .rasterizer.function import check_background, rasterize_channels, rasterize_with_tiles
 from .spherical_harmonics import evaluate_sh_at
 from .torch_lib.projection import ndc_depth
 
@@ -158,7 +158,8 @@ def _refuse_float64(gaussians, camera_params) -> None:
 
 def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config: RasterConfig = RasterConfig(),
                      use_sh: bool = False, render_depth: bool = False, use_depth16: bool = False,
-                     render_median_depth: bool = False, sparse_grad: bool = False) -> Rendering:
+                     render_median_depth: bool = False, background: Optional[torch.Tensor] = None,
+                     differentiable_weight: bool = False, sparse_grad: bool = False) -> Rendering:
     """Render one view.  `gaussians.feature` holds (N, C) features, or (N, 3, (D+1)^2) SH coefficients with
     use_sh=True.  render_depth adds depth and depth variance images, render_median_depth a second,
     non-blended pass that picks the depth at half opacity, use_depth16 sorts on 16-bit depth codes.
@@ -169,16 +170,33 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
     that are zero outside the view; the optimizers of `optim` step from them directly.  The camera gradients stay
     dense.  Only frames the fused node covers (SH colours, or plain features up to 30 channels): anything else raises
     NotImplementedError (CPU or non-float32 tensors raise the operators' device or dtype error first); an empty scene
-    (N = 0) has no rows and renders as without the switch.  Rendered values are the same either way."""
+    (N = 0) has no rows and renders as without the switch.  Rendered values are the same either way.
+
+    background, differentiable_weight (not arguments of the reference either; pass them by keyword).  background: a
+    (C,) colour, float32 on the device of the features, C the number of colour channels of `image` (the two depth
+    channels of render_depth do not count).  The returned image is composited on it inside the rasterizer, image =
+    blend + (1 - image_weight) * background; image_weight itself does not change.  It may require grad and then
+    receives dL/dbackground.  (A per-pixel background is composited by the caller in torch -- correctly once
+    differentiable_weight is set.)  differentiable_weight=True: image_weight takes part in autograd, so alpha, mask and
+    sky losses reach the Gaussians.  `depth` and `depth_var` of render_depth keep treating the weight in their divisor
+    as a constant, and are the same with and without a background; the median-depth pass has no background.  Both
+    arguments need config.use_alpha_blending (ValueError); a background of another dtype or device raises TypeError,
+    one of another shape AssertionError.  They work with sparse_grad."""
     _check_call(gaussians, camera_params, config, dict(use_sh=use_sh, render_depth=render_depth,
                                                       use_depth16=use_depth16,
                                                       render_median_depth=render_median_depth,
-                                                      sparse_grad=sparse_grad))
+                                                      sparse_grad=sparse_grad,
+                                                      differentiable_weight=differentiable_weight))
     _refuse_float64(gaussians, camera_params)
+    if background is not None or differentiable_weight:
+        feature = gaussians.feature
+        check_background(background, differentiable_weight, config, feature,
+                         feature.shape[1] if feature.ndim >= 2 else 0, "render_gaussians")
     from .fused import fused_supported, render_fused
     if fused_supported(gaussians, camera_params, use_sh, render_median_depth):
         return render_fused(gaussians, camera_params, config, render_depth, use_depth16,
-                            render_median_depth=render_median_depth, sparse_grad=sparse_grad)
+                            render_median_depth=render_median_depth, sparse_grad=sparse_grad,
+                            background=background, differentiable_weight=differentiable_weight)
     feature = gaussians.feature
     if sparse_grad and gaussians.position.shape[0] > 0:
         # an empty scene has no rows to be sparse over and renders as it always did; tensors that are not float32 on
@@ -199,7 +217,8 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
         assert colours.dim() == 2, f"Features must be (N, C) if use_sh=False, got {colours.shape}"
     return render_projected(visible, splats, colours, depths, camera_params, config, render_depth=render_depth,
                             use_depth16=use_depth16, render_median_depth=render_median_depth,
-                            ndc_depths=sort_depths)
+                            ndc_depths=sort_depths, background=background,
+                            differentiable_weight=differentiable_weight)
 
 
 def compute_depth_variance(depth_depthsq: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6):
@@ -212,10 +231,15 @@ def compute_depth_variance(depth_depthsq: torch.Tensor, weight: torch.Tensor, ep
 def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features: torch.Tensor, depths: torch.Tensor,
                      camera_params: CameraParams, config: RasterConfig, render_depth: bool = False,
                      use_depth16: bool = False, render_median_depth: bool = False, use_ndc_depth: bool = False,
-                     ndc_depths: Optional[torch.Tensor] = None) -> Rendering:
+                     ndc_depths: Optional[torch.Tensor] = None, background: Optional[torch.Tensor] = None,
+                     differentiable_weight: bool = False) -> Rendering:
     """Tile-map and rasterize splats that are already projected.  `ndc_depths` (the sort depth) comes from the
-    projection kernel when the caller has it; otherwise it is derived from `depths` here."""
+    projection kernel when the caller has it; otherwise it is derived from `depths` here.  background (C,) over the
+    channels of `features`, differentiable_weight: see render_gaussians."""
     size = camera_params.image_size
+    if isinstance(features, torch.Tensor) and features.ndim == 2 and isinstance(config, RasterConfig):
+        # refused before the tile mapper launches anything
+        check_background(background, differentiable_weight, config, features, features.shape[1], "render_projected")
     if ndc_depths is None:
         ndc_depths = ndc_depth(depths.detach(), camera_params.near_plane, camera_params.far_plane)
     channels = features
@@ -232,7 +256,10 @@ def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features:
     overlap_to_point, tile_ranges = map_to_tiles(gaussians2d, ndc_depths, image_size=size, config=config,
                                                  use_depth16=use_depth16)
     tiles = dict(tile_overlap_ranges=tile_ranges.view(-1, 2), overlap_to_point=overlap_to_point, image_size=size)
-    raster = rasterize_with_tiles(gaussians2d, channels, config=raster_config, **tiles)
+    # the background covers the feature channels only: z and z^2 composite on 0
+    raster = rasterize_channels(gaussians2d, channels, config=raster_config, background=background,
+                                background_offset=channels.shape[1] - features.shape[1],
+                                differentiable_weight=differentiable_weight, **tiles)
 
     median = None
     if render_median_depth:  # first splat that takes a pixel past half opacity, no blending
@@ -241,7 +268,8 @@ def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features:
 
     image, mean_z, var_z = raster.image, None, None
     if render_depth:
-        mean_z, var_z = compute_depth_variance(image[..., :2], raster.image_weight)
+        # the divisor is a constant of the backward, also when image_weight is differentiable
+        mean_z, var_z = compute_depth_variance(image[..., :2], raster.image_weight.detach())
         image = image[..., 2:]
     return Rendering(image=image, image_weight=raster.image_weight, depth=mean_z, depth_var=var_z, median_depth=median,
                      camera=camera_params, config=config, points_in_view=indexes, point_depth=depths,
