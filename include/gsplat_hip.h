@@ -325,11 +325,26 @@ int gs_find_ranges(int64_t k, const uint64_t* sorted_keys, int32_t use_depth16, 
  * first *heavy_tiles tiles of the order are rasterized by four workgroups each (one per 8x8 quadrant; tile_size
  * 16 only, ignored otherwise) so that no single wave walks a very full tile alone.  Results depend on neither.
  * shard (optional, see GsRowShard): tile ids are local, image / alpha hold the owned pixel rows only.
+ *
+ * Background colour and differentiable weight image (no reference counterpart: the reference composites in torch and
+ * marks the weight non-differentiable).  With T = 1 - alpha the transmittance a pixel's walk ended with:
+ *   forward:  image_c = sum_i w_i f_ic + T * background[c - background_offset]  for c >= background_offset, composited in
+ *             the kernel's epilogue; channels below background_offset (the depth features of a depth render) composite on
+ *             0.  background (device, num_features - background_offset floats) may be NULL; alpha is unchanged.
+ *   backward: image is the forward's (composited) image; grad_weight (H,W; optional) is dL/d alpha and needs the
+ *             forward's alpha image (alpha may be NULL without it).  Both enter through each pixel's initial remaining
+ *             colour only, R0 = sum_c image_c g_c - T grad_weight, because dT/d alpha_i = -T / (1 - alpha_i); the
+ *             heuristics follow from the corrected dL/d alpha.  dL/d background_c = sum_pixels g_c T is left to the
+ *             caller.
+ * A background with cfg->use_alpha_blending = 0 returns GS_ERR_UNSUPPORTED, a background_offset outside [0, F) or a
+ * grad_weight without alpha GS_ERR_INVALID_ARGUMENT, before any launch.  The _wide and _f64 pairs below take the same
+ * arguments with the same meaning.
  */
 int gs_raster_fwd(int64_t v, int32_t num_features, const float* points, const float* features,
                   const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                   int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order, const int32_t* heavy_tiles,
-                  float* image, float* alpha, float* visibility, const GsRowShard* shard, void* stream);
+                  float* image, float* alpha, float* visibility, const GsRowShard* shard, const float* background,
+                  int32_t background_offset, void* stream);
 
 /* replaces: rasterizer/backward.py:53-228 _backward_kernel.
  * Per-Gaussian gradients are accumulated with float atomics into ONE row per Gaussian,
@@ -343,34 +358,10 @@ int32_t gs_grad_row_floats(int32_t num_features);
 int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const float* features,
                   const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                   int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order, const int32_t* heavy_tiles,
-                  const float* image, const float* grad_image, float* grad_rows, const GsRowShard* shard,
-                  void* stream);
+                  const float* image, const float* grad_image, const float* alpha, const float* grad_weight,
+                  float* grad_rows, const GsRowShard* shard, void* stream);
 int gs_raster_bwd_unpack(int64_t v, int32_t num_features, const float* grad_rows, float* grad_points,
                          float* grad_features, float* point_heuristic, void* stream);
-
-/* Background colour and differentiable weight image (no reference counterpart: the reference composites in torch and
- * marks the weight non-differentiable).  With T = 1 - alpha the transmittance a pixel's walk ended with:
- *   forward:  image_c = sum_i w_i f_ic + T * background[c - background_offset]  for c >= background_offset, composited in
- *             the kernel's epilogue; channels below background_offset (the depth features of a depth render) composite on
- *             0.  background (device, num_features - background_offset floats) may be NULL; alpha is unchanged.
- *   backward: image is the forward's (composited) image; grad_weight (H,W; optional) is dL/d alpha and needs the
- *             forward's alpha image.  Both enter through each pixel's initial remaining colour only,
- *             R0 = sum_c image_c g_c - T grad_weight, because dT/d alpha_i = -T / (1 - alpha_i); the heuristics follow
- *             from the corrected dL/d alpha.  dL/d background_c = sum_pixels g_c T is left to the caller.
- * A background with cfg->use_alpha_blending = 0 returns GS_ERR_UNSUPPORTED, a background_offset outside [0, F) or a
- * grad_weight without alpha GS_ERR_INVALID_ARGUMENT, before any launch.  gs_raster_fwd / gs_raster_bwd (and the _wide
- * and _f64 pairs below) are these calls with NULLs.
- */
-int gs_raster_fwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                     int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order, const int32_t* heavy_tiles,
-                     float* image, float* alpha, float* visibility, const GsRowShard* shard, const float* background,
-                     int32_t background_offset, void* stream);
-int gs_raster_bwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                     int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order, const int32_t* heavy_tiles,
-                     const float* image, const float* grad_image, const float* alpha, const float* grad_weight,
-                     float* grad_rows, const GsRowShard* shard, void* stream);
 
 /* Wide features: the forward and backward above for 1 <= num_features <= GS_MAX_WIDE_FEATURES (features lifted from
  * 2D models), honouring every GsRasterConfig field gs_raster_fwd / gs_raster_bwd honour.  No tile order, heavy-tile
@@ -381,21 +372,12 @@ int gs_raster_bwd_bg(int64_t v, int32_t num_features, const float* points, const
 int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
                        const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                        int32_t height, const GsRasterConfig* cfg, float* image, float* alpha, float* visibility,
-                       void* stream);
+                       const float* background, int32_t background_offset, void* stream);
 int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
                        const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                        int32_t height, const GsRasterConfig* cfg, const float* image, const float* grad_image,
-                       float* grad_points, float* grad_features, float* point_heuristic, void* stream);
-/* ... with a background / a gradient of the weight image: see gs_raster_fwd_bg / gs_raster_bwd_bg */
-int gs_raster_fwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                          const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                          int32_t height, const GsRasterConfig* cfg, float* image, float* alpha, float* visibility,
-                          const float* background, int32_t background_offset, void* stream);
-int gs_raster_bwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                          const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                          int32_t height, const GsRasterConfig* cfg, const float* image, const float* grad_image,
-                          const float* alpha, const float* grad_weight, float* grad_points, float* grad_features,
-                          float* point_heuristic, void* stream);
+                       const float* alpha, const float* grad_weight, float* grad_points, float* grad_features,
+                       float* point_heuristic, void* stream);
 
 /* ------------------------------------------------- plain features (render_gaussians(use_sh=False)) --
  * replaces: `features = gaussians.feature[indexes]` (renderer.py:166) and its index backward, inside the fused frame:
@@ -445,18 +427,29 @@ int gs_depth_split_bwd(int64_t pixels, int32_t channels, const float* depth, con
  *   counts_host (optional, pinned host int32[5]) as in gs_map_prepare: {K, fullest tile, overflow, heavy, V}.
  *   counts_event (optional, a hipEvent_t): recorded on `stream` right behind the mapper's scan, i.e. when counts_host is
  *     final -- the caller waits on it for V and K while the sort and the rasterizer are still running.
+ *   gs_frame_fwd: background (device, `channels` floats, may be NULL) is composited under the colour channels in the
+ *     rasterizer's epilogue (gs_raster_fwd); the depth features of render_depth composite on 0, so depth and depth_var
+ *     do not change, and the median-depth pass has no background.
  *   gs_frame_bwd: v, k = the counts read back; grad_image (H, W, C) and, with render_depth, grad_img_depth /
- *     grad_img_var (H, W) -- any may be NULL (zero); attached_points (v, 7) / attached_depth (v): gradients the caller
- *     attached to the projected splats / depths themselves (optional).  Outputs: dense parameter gradients
+ *     grad_img_var (H, W) -- any may be NULL (zero); grad_weight (local_height x width, may be NULL) is dL/d alpha
+ *     (gs_raster_bwd): it reads the workspace's alpha image and needs a grad_image (zeros will do), and the divisor of
+ *     depth / depth_var keeps treating alpha as a constant; attached_points (v, 7) / attached_depth (v): gradients the
+ *     caller attached to the projected splats / depths themselves (optional).  Outputs: dense parameter gradients
  *     d_position (n,3), d_log_scaling (n,3), d_rotation (n,4), d_alpha_logit (n,1), d_feature (n,C[,D]);
  *     d_T_camera_world (16) / d_projection (4) optional; d_camera_centre (3, optional, ZEROED BY THE CALLER) receives
  *     the SH view direction's gradient with respect to the camera centre.
- *   gs_frame_bwd_part: gs_frame_bwd with a trailing `part` (GsFrameBwdPart; NULL = gs_frame_bwd): run the stages
- *     [first_stage, end_stage) of GS_BWD_* only -- RASTER (clears the gradient rows unless prepare_backward did),
- *     COLOURS (SH / feature-gather adjoint from colour_grads), PROJECT (adds the attached gradients into splat_grads,
- *     then the projection adjoint) -- on the Gaussians [row_begin, row_end), whose gradients fill outputs of
- *     row_end - row_begin rows.  A sharded frame exchanges its partial gradients between RASTER and COLOURS, so no
- *     call of it may run both (gs_frame_bwd, which runs every stage, refuses sharded frames).
+ *     part (GsFrameBwdPart; NULL = every stage on all rows): run the stages [first_stage, end_stage) of GS_BWD_* only
+ *     -- RASTER (clears the gradient rows unless prepare_backward did), COLOURS (SH / feature-gather adjoint from
+ *     colour_grads), PROJECT (adds the attached gradients into splat_grads, then the projection adjoint) -- on the
+ *     Gaussians [row_begin, row_end), whose gradients fill outputs of row_end - row_begin rows.  A sharded frame
+ *     exchanges its partial gradients between RASTER and COLOURS, so no call of it may run both (a NULL part, which
+ *     runs every stage, is refused for a sharded frame).
+ *   gs_frame_bwd_rows: gs_frame_bwd with ROW-COMPACT parameter gradients (sparse visible-row gradients; no reference
+ *     counterpart): d_position (v,3), d_log_scaling (v,3), d_rotation (v,4), d_alpha_logit (v,1), d_feature (v,C[,D]),
+ *     row i for Gaussian indexes[i] of the frame's visible list (layout.indexes) -- the adjoints are gs_sh_bwd_rows /
+ *     gs_feature_gather_bwd_rows and gs_project_bwd_rows, nothing of size n is written.  Same arguments, so a caller
+ *     may run RASTER / COLOURS / PROJECT in separate calls.  Refuses a sharded frame and a row sub-range (row_begin,
+ *     row_end other than 0, n) with GS_ERR_UNSUPPORTED.  The camera gradients stay dense.
  */
 typedef struct GsFrame {
   int64_t n;
@@ -493,8 +486,8 @@ typedef struct GsFrameLayout {
 } GsFrameLayout;
 
 /* Optional per-stage timing of the frame calls: stage_events is a HOST array of 2 * GS_FWD_STAGES (gs_frame_fwd) or
- * 2 * GS_BWD_STAGES (gs_frame_bwd[_part]) hipEvent_t handles; entry 2 k is recorded in front of stage k and 2 k + 1 behind it, on
- * `stream`; NULL entries (or a NULL array) are skipped.  This is how a caller measures one kernel's launch time with HIP
+ * 2 * GS_BWD_STAGES (gs_frame_bwd, gs_frame_bwd_rows) hipEvent_t handles; entry 2 k is recorded in front of stage k and
+ * 2 k + 1 behind it, on `stream`; NULL entries (or a NULL array) are skipped.  This is how a caller measures one kernel's launch time with HIP
  * events on the launch stream although the whole direction is one call (bench.py's roofline). */
 enum { GS_FWD_PROJECT = 0, GS_FWD_COLOURS, GS_FWD_MAP_PREPARE, GS_FWD_MAP_FINISH, GS_FWD_RASTER, GS_FWD_STAGES };
 enum { GS_BWD_RASTER = 0, GS_BWD_COLOURS, GS_BWD_PROJECT, GS_BWD_STAGES };
@@ -511,65 +504,23 @@ int gs_frame_layout(const GsFrame* frame, GsFrameLayout* layout);
 int gs_frame_fwd(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
                  const float* alpha_logit, const float* feature, const float* T_camera_world, const float* projection,
                  void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int32_t* counts_host,
-                 void* counts_event, void* const* stage_events, void* stream);
+                 void* counts_event, void* const* stage_events, const float* background, void* stream);
 int gs_frame_bwd(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
                  const float* alpha_logit, const float* feature, const float* T_camera_world, const float* projection,
                  void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
                  const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
-                 const float* attached_points, const float* attached_depth, float* d_position, float* d_log_scaling,
-                 float* d_rotation, float* d_alpha_logit, float* d_feature, float* d_T_camera_world,
-                 float* d_projection, float* d_camera_centre, void* const* stage_events, void* stream);
-int gs_frame_bwd_part(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
-                      const float* alpha_logit, const float* feature, const float* T_camera_world,
-                      const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                      int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image, const float* grad_img_depth,
-                      const float* grad_img_var, const float* attached_points, const float* attached_depth,
-                      float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
-                      float* d_feature, float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                      void* const* stage_events, void* stream, const GsFrameBwdPart* part);
-/* gs_frame_bwd_rows: gs_frame_bwd_part with ROW-COMPACT parameter gradients (sparse visible-row gradients; no reference
- * counterpart): d_position (v,3), d_log_scaling (v,3), d_rotation (v,4), d_alpha_logit (v,1), d_feature (v,C[,D]), row i
- * for Gaussian indexes[i] of the frame's visible list (layout.indexes) -- the adjoints are gs_sh_bwd_rows /
- * gs_feature_gather_bwd_rows and gs_project_bwd_rows, nothing of size n is written.  Same trailing `part` (NULL = every
- * stage), so a caller may run RASTER / COLOURS / PROJECT in separate calls.  Refuses a sharded frame and a row
- * sub-range (row_begin, row_end other than 0, n) with GS_ERR_UNSUPPORTED.  The camera gradients stay dense. */
+                 const float* grad_weight, const float* attached_points, const float* attached_depth,
+                 float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                 float* d_T_camera_world, float* d_projection, float* d_camera_centre, void* const* stage_events,
+                 const GsFrameBwdPart* part, void* stream);
 int gs_frame_bwd_rows(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
                       const float* alpha_logit, const float* feature, const float* T_camera_world,
                       const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
                       int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image, const float* grad_img_depth,
-                      const float* grad_img_var, const float* attached_points, const float* attached_depth,
-                      float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
-                      float* d_feature, float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                      void* const* stage_events, void* stream, const GsFrameBwdPart* part);
-/* The frame with a background colour and a differentiable weight image (gs_raster_fwd_bg / gs_raster_bwd_bg).
- * gs_frame_fwd_bg: background (device, `channels` floats, may be NULL) is composited under the colour channels in the
- * rasterizer's epilogue; the depth features of render_depth composite on 0, so depth and depth_var do not change, and
- * the median-depth pass has no background.  gs_frame_bwd_part_bg / gs_frame_bwd_rows_bg: grad_weight (local_height x
- * width, may be NULL) is dL/d alpha; it reads the workspace's alpha image and needs a grad_image (zeros will do).  The
- * divisor of depth / depth_var keeps treating alpha as a constant.  The entry points above are these with NULLs. */
-int gs_frame_fwd_bg(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
-                    const float* alpha_logit, const float* feature, const float* T_camera_world,
-                    const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                    int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
-                    const float* background, void* stream);
-int gs_frame_bwd_part_bg(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
-                         const float* alpha_logit, const float* feature, const float* T_camera_world,
-                         const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                         int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
-                         const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
-                         const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
-                         float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
-                         float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part,
-                         const float* grad_weight);
-int gs_frame_bwd_rows_bg(const GsFrame* frame, const float* position, const float* log_scaling, const float* rotation,
-                         const float* alpha_logit, const float* feature, const float* T_camera_world,
-                         const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                         int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
-                         const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
-                         const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
-                         float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
-                         float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part,
-                         const float* grad_weight);
+                      const float* grad_img_var, const float* grad_weight, const float* attached_points,
+                      const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
+                      float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
+                      float* d_camera_centre, void* const* stage_events, const GsFrameBwdPart* part, void* stream);
 
 /* ------------------------------------------------------------------- Morton ordering --
  * replaces: misc/morton_sort.py:78-88 code_points64_kernel (Grid.morton_code64, :37-66).  points (n,3);
@@ -673,23 +624,13 @@ int64_t gs_raster_f64_scratch_bytes(int64_t v, int64_t k, int32_t num_features);
 int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
                       const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                       int32_t height, const GsRasterConfigF64* cfg, double* image, double* alpha,
-                      double* visibility, void* scratch, int64_t scratch_bytes, void* stream);
+                      double* visibility, const double* background, int32_t background_offset, void* scratch,
+                      int64_t scratch_bytes, void* stream);
 int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
                       const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
                       int32_t height, const GsRasterConfigF64* cfg, const double* image, const double* grad_image,
-                      double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
-                      int64_t scratch_bytes, void* stream);
-/* ... with a background / a gradient of the weight image: see gs_raster_fwd_bg / gs_raster_bwd_bg */
-int gs_raster_fwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
-                         const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                         int32_t height, const GsRasterConfigF64* cfg, double* image, double* alpha,
-                         double* visibility, const double* background, int32_t background_offset, void* scratch,
-                         int64_t scratch_bytes, void* stream);
-int gs_raster_bwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
-                         const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                         int32_t height, const GsRasterConfigF64* cfg, const double* image, const double* grad_image,
-                         const double* alpha, const double* grad_weight, double* grad_points, double* grad_features,
-                         double* point_heuristic, void* scratch, int64_t scratch_bytes, void* stream);
+                      const double* alpha, const double* grad_weight, double* grad_points, double* grad_features,
+                      double* point_heuristic, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* -------------------------------------------------------------------- photometric loss --
  * (1 - ssim_weight) * mean|x - y| + ssim_weight * (1 - SSIM(x, y)) on channel-last images, x = image (the render),

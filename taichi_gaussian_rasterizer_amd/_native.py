@@ -65,7 +65,7 @@ class GsFrameLayout(ctypes.Structure):
 
 
 class GsFrameBwdPart(ctypes.Structure):
-    """include/gsplat_hip.h GsFrameBwdPart: the stages and Gaussian rows one gs_frame_bwd_part call runs, and where its
+    """include/gsplat_hip.h GsFrameBwdPart: the stages and Gaussian rows one gs_frame_bwd call runs, and where its
     adjoints read the colour / splat gradients (NULL = the frame's gradient rows)"""
     _fields_ = [("first_stage", c_int32), ("end_stage", c_int32), ("colour_grads", c_void_p),
                 ("splat_grads", c_void_p), ("colour_stride", c_int32), ("splat_stride", c_int32),
@@ -84,6 +84,10 @@ _FRAME = POINTER(GsFrame)
 _SHARD = POINTER(GsRowShard)
 _P = c_void_p
 _I32, _I64, _F64 = c_int32, c_int64, c_double
+
+# gs_frame_bwd and gs_frame_bwd_rows: frame, 7 inputs, workspace and scratch with their sizes, v, k, 4 image gradients,
+# 2 attached gradients, 8 outputs, stage_events, part, stream
+_FRAME_BWD = [_FRAME] + [_P] * 8 + [_I64, _P, _I64, _I64, _I64] + [_P] * 15 + [POINTER(GsFrameBwdPart), _P]
 
 # name -> (restype, argtypes); every symbol declared in include/gsplat_hip.h
 SIGNATURES = {
@@ -120,14 +124,15 @@ SIGNATURES = {
     "gs_radix_sort_pairs": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I32, _I32, _P, _I64, _P]),
     "gs_find_ranges": (ctypes.c_int, [_I64, _P, _I32, _I64, _P, _P]),
     "gs_raster_fwd": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _SHARD,
-                                      _P]),
+                                      _P, _I32, _P]),
     "gs_grad_row_floats": (_I32, [_I32]),
-    "gs_raster_bwd": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _SHARD,
-                                      _P]),
+    "gs_raster_bwd": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _P, _P,
+                                      _SHARD, _P]),
     "gs_raster_bwd_unpack": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _P]),
-    "gs_raster_fwd_wide": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P]),
-    "gs_raster_bwd_wide": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P,
+    "gs_raster_fwd_wide": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _I32,
                                            _P]),
+    "gs_raster_bwd_wide": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _P,
+                                           _P, _P]),
     "gs_segmented_sort_pairs": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P]),
     "gs_optim_visibility_weights": (ctypes.c_int, [_I64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P]),
     "gs_optim_step": (ctypes.c_int, [_I32, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float,
@@ -138,19 +143,15 @@ SIGNATURES = {
     "gs_depth_split_fwd": (ctypes.c_int, [_I64, _I32, _P, _P, c_float, _P, _P, _P, _P]),
     "gs_depth_split_bwd": (ctypes.c_int, [_I64, _I32, _P, _P, c_float, _P, _P, _P, _P, _P]),
     "gs_frame_layout": (ctypes.c_int, [_FRAME, POINTER(GsFrameLayout)]),
-    "gs_frame_fwd": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P]),
-    "gs_frame_bwd": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P,
-                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gs_frame_bwd_part": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
-                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(GsFrameBwdPart)]),
+    "gs_frame_fwd": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "gs_frame_bwd": (ctypes.c_int, _FRAME_BWD),
     # sparse visible-row gradients: row-compact adjoints, their frame call and the optimizer step that reads them
     "gs_project_bwd_rows_scratch_bytes": (_I64, [_I64]),
     "gs_project_bwd_rows": (ctypes.c_int, [_I64, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _CFG, _P, _P, _I32, _P, _P,
                                             _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "gs_sh_bwd_rows": (ctypes.c_int, [_I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "gs_feature_gather_bwd_rows": (ctypes.c_int, [_I64, _I32, _P, _I32, _P, _P]),
-    "gs_frame_bwd_rows": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
-                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(GsFrameBwdPart)]),
+    "gs_frame_bwd_rows": (ctypes.c_int, _FRAME_BWD),
     "gs_optim_grad_rows": (ctypes.c_int, [_I64, _P, _I64, _P, _P, _P]),
     "gs_optim_step_rows": (ctypes.c_int, [_I32, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, c_float, c_float,
                                            c_float, c_float, _I32, _P, _P, _P, _P, _P, _P]),
@@ -164,30 +165,10 @@ SIGNATURES = {
     "gs_sh_bwd_f64_scratch_bytes": (_I64, [_I64, _I64]),
     "gs_sh_bwd_f64": (ctypes.c_int, [_I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "gs_raster_f64_scratch_bytes": (_I64, [_I64, _I64, _I32]),
-    "gs_raster_fwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _I64,
-                                          _P]),
-    "gs_raster_bwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P, _P,
+    "gs_raster_fwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _I32, _P,
                                           _I64, _P]),
-    # background colour and differentiable weight image: the entry points above are these with NULLs
-    "gs_raster_fwd_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _SHARD,
-                                         _P, _I32, _P]),
-    "gs_raster_bwd_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _P, _P,
-                                         _SHARD, _P]),
-    "gs_raster_fwd_wide_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _I32,
-                                              _P]),
-    "gs_raster_bwd_wide_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG, _P, _P, _P, _P, _P, _P,
-                                              _P, _P]),
-    "gs_raster_fwd_f64_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _I32,
-                                             _P, _I64, _P]),
-    "gs_raster_bwd_f64_bg": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P,
-                                             _P, _P, _P, _I64, _P]),
-    "gs_frame_fwd_bg": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
-    "gs_frame_bwd_part_bg": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
-                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                             POINTER(GsFrameBwdPart), _P]),
-    "gs_frame_bwd_rows_bg": (ctypes.c_int, [_FRAME, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P,
-                                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                             POINTER(GsFrameBwdPart), _P]),
+    "gs_raster_bwd_f64": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _CFG64, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _I64, _P]),
     "gs_ssim_window": (ctypes.c_int, [_I32, _F64, POINTER(c_float)]),
     "gs_photo_loss_scratch_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "gs_photo_loss_fwd": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _F64,
@@ -259,8 +240,7 @@ class _TimedLib:
     def __getattr__(self, name):  # first lookup only: the result is stored on the instance
         fn = getattr(self._h, name)
         if name.endswith("_bytes") or name in ("gs_last_error", "gs_version", "gs_grad_row_floats", "gs_frame_layout",
-                                               "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_part", "gs_frame_bwd_rows",
-                                               "gs_frame_fwd_bg", "gs_frame_bwd_part_bg", "gs_frame_bwd_rows_bg",
+                                               "gs_frame_fwd", "gs_frame_bwd", "gs_frame_bwd_rows",
                                                "gs_map_touched_offset", "gs_ssim_window"):
             setattr(self, name, fn)
             return fn

@@ -16,7 +16,7 @@ void gs_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* gs_last_error(void) { return g_error; }
-extern "C" int gs_version(void) { return 6; }
+extern "C" int gs_version(void) { return 7; }
 
 // see gs_common.h.  Measured crossovers (tools/exp_nb.py, tools/exp_shard_nb.py): the forward (lighter per overlap,
 // more latency-bound) wants the extra waves up to larger grids than the backward.

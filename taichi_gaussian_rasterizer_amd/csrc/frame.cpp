@@ -139,11 +139,11 @@ extern "C" int gs_frame_layout(const GsFrame* f, GsFrameLayout* out) {
   return GS_OK;
 }
 
-extern "C" int gs_frame_fwd_bg(const GsFrame* f, const float* position, const float* log_scaling,
-                               const float* rotation, const float* alpha_logit, const float* feature,
-                               const float* T_camera_world, const float* projection, void* workspace,
-                               int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int32_t* counts_host,
-                               void* counts_event, void* const* stage_events, const float* background, void* stream) {
+extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
+                            const float* alpha_logit, const float* feature, const float* T_camera_world,
+                            const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                            int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
+                            const float* background, void* stream) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
@@ -278,8 +278,8 @@ extern "C" int gs_frame_fwd_bg(const GsFrame* f, const float* position, const fl
   tm.mark(GS_FWD_MAP_FINISH, 1, stream);
   tm.mark(GS_FWD_RASTER, 0, stream);
   // the background applies to the colour channels only: the depth features [0, col0) composite on 0
-  if ((rc = gs_raster_fwd_bg(d.n, d.F, points, feats, tile_ranges, o2p, f->k_capacity, f->width, f->height, &rcfg,
-                             tile_order, counts + 7, image, alpha, vis, shard, background, d.col0, stream)))
+  if ((rc = gs_raster_fwd(d.n, d.F, points, feats, tile_ranges, o2p, f->k_capacity, f->width, f->height, &rcfg,
+                          tile_order, counts + 7, image, alpha, vis, shard, background, d.col0, stream)))
     return rc;
   tm.mark(GS_FWD_RASTER, 1, stream);
   if (f->render_depth &&
@@ -296,7 +296,7 @@ extern "C" int gs_frame_fwd_bg(const GsFrame* f, const float* position, const fl
     pick.compute_point_heuristic = 0;
     if ((rc = gs_raster_fwd(d.n, 1, points, depth, tile_ranges, o2p, f->k_capacity, f->width, f->height, &pick,
                             tile_order, counts + 7, at<float>(workspace, L.median),
-                            at<float>(scratch, L.s_median_cover), nullptr, shard, stream)))
+                            at<float>(scratch, L.s_median_cover), nullptr, shard, nullptr, 0, stream)))
       return rc;
   }
   return tm.rc;
@@ -304,16 +304,15 @@ extern "C" int gs_frame_fwd_bg(const GsFrame* f, const float* position, const fl
 
 namespace {
 
-// gs_frame_bwd_part (compact = false: (n, ...) gradients, zero rows for the culled Gaussians) and gs_frame_bwd_rows
+// gs_frame_bwd (compact = false: (n, ...) gradients, zero rows for the culled Gaussians) and gs_frame_bwd_rows
 // (compact = true: (v, ...) gradients, row i for Gaussian indexes[i])
 int frame_bwd(bool compact, const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
               const float* alpha_logit, const float* feature, const float* T_camera_world, const float* projection,
               void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
-              const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
+              const float* grad_image, const float* grad_img_depth, const float* grad_img_var, const float* grad_weight,
               const float* attached_points, const float* attached_depth, float* d_position, float* d_log_scaling,
               float* d_rotation, float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
-              float* d_camera_centre, void* const* stage_events, void* stream, const GsFrameBwdPart* part,
-              const float* grad_weight) {
+              float* d_camera_centre, void* const* stage_events, const GsFrameBwdPart* part, void* stream) {
   StageTimer tm{stage_events};
   Dims d;
   if (int rc = frame_dims(f, &d)) return rc;
@@ -373,11 +372,11 @@ int frame_bwd(bool compact, const GsFrame* f, const float* position, const float
     }
     tm.mark(GS_BWD_RASTER, 0, stream);
     if (g_img && v > 0 && d.P > 0 && k > 0 &&
-        (rc = gs_raster_bwd_bg(v, d.F, at<float>(workspace, L.points), feats, at<int32_t>(workspace, L.tile_ranges),
-                               at<int32_t>(workspace, L.overlap_to_point), k, f->width, f->height, cfg,
-                               at<int32_t>(workspace, L.tile_order), counts + 7, at<float>(workspace, L.image), g_img,
-                               grad_weight ? at<float>(workspace, L.alpha) : nullptr, grad_weight, rows,
-                               f->has_shard ? &f->shard : nullptr, stream)))
+        (rc = gs_raster_bwd(v, d.F, at<float>(workspace, L.points), feats, at<int32_t>(workspace, L.tile_ranges),
+                            at<int32_t>(workspace, L.overlap_to_point), k, f->width, f->height, cfg,
+                            at<int32_t>(workspace, L.tile_order), counts + 7, at<float>(workspace, L.image), g_img,
+                            grad_weight ? at<float>(workspace, L.alpha) : nullptr, grad_weight, rows,
+                            f->has_shard ? &f->shard : nullptr, stream)))
       return rc;
     tm.mark(GS_BWD_RASTER, 1, stream);
   }
@@ -429,91 +428,32 @@ int frame_bwd(bool compact, const GsFrame* f, const float* position, const float
 
 }  // namespace
 
-extern "C" int gs_frame_bwd_part_bg(const GsFrame* f, const float* position, const float* log_scaling,
-                                 const float* rotation, const float* alpha_logit, const float* feature,
-                                 const float* T_camera_world, const float* projection, void* workspace,
-                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
-                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
-                                 const float* attached_points, const float* attached_depth, float* d_position,
-                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
-                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part,
-                                    const float* grad_weight) {
-  return frame_bwd(false, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
-                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
-                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
-                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part, grad_weight);
-}
-
-extern "C" int gs_frame_bwd_rows_bg(const GsFrame* f, const float* position, const float* log_scaling,
-                                 const float* rotation, const float* alpha_logit, const float* feature,
-                                 const float* T_camera_world, const float* projection, void* workspace,
-                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
-                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
-                                 const float* attached_points, const float* attached_depth, float* d_position,
-                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
-                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part,
-                                    const float* grad_weight) {
-  return frame_bwd(true, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
-                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var,
-                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
-                   d_T_camera_world, d_projection, d_camera_centre, stage_events, stream, part, grad_weight);
-}
-
-extern "C" int gs_frame_bwd_part(const GsFrame* f, const float* position, const float* log_scaling,
-                                 const float* rotation, const float* alpha_logit, const float* feature,
-                                 const float* T_camera_world, const float* projection, void* workspace,
-                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
-                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
-                                 const float* attached_points, const float* attached_depth, float* d_position,
-                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
-                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
-  return gs_frame_bwd_part_bg(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
-                              workspace, workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth,
-                              grad_img_var, attached_points, attached_depth, d_position, d_log_scaling, d_rotation,
-                              d_alpha_logit, d_feature, d_T_camera_world, d_projection, d_camera_centre, stage_events,
-                              stream, part, nullptr);
-}
-
-extern "C" int gs_frame_bwd_rows(const GsFrame* f, const float* position, const float* log_scaling,
-                                 const float* rotation, const float* alpha_logit, const float* feature,
-                                 const float* T_camera_world, const float* projection, void* workspace,
-                                 int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, int64_t v, int64_t k,
-                                 const float* grad_image, const float* grad_img_depth, const float* grad_img_var,
-                                 const float* attached_points, const float* attached_depth, float* d_position,
-                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
-                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
-                                 void* const* stage_events, void* stream, const GsFrameBwdPart* part) {
-  return gs_frame_bwd_rows_bg(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
-                              workspace, workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth,
-                              grad_img_var, attached_points, attached_depth, d_position, d_log_scaling, d_rotation,
-                              d_alpha_logit, d_feature, d_T_camera_world, d_projection, d_camera_centre, stage_events,
-                              stream, part, nullptr);
-}
-
-extern "C" int gs_frame_fwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
-                            const float* alpha_logit, const float* feature, const float* T_camera_world,
-                            const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
-                            int64_t scratch_bytes, int32_t* counts_host, void* counts_event, void* const* stage_events,
-                            void* stream) {
-  return gs_frame_fwd_bg(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
-                         workspace_bytes, scratch, scratch_bytes, counts_host, counts_event, stage_events, nullptr,
-                         stream);
-}
-
 extern "C" int gs_frame_bwd(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
                             const float* alpha_logit, const float* feature, const float* T_camera_world,
                             const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
                             int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
-                            const float* grad_img_depth, const float* grad_img_var, const float* attached_points,
-                            const float* attached_depth, float* d_position, float* d_log_scaling, float* d_rotation,
-                            float* d_alpha_logit, float* d_feature, float* d_T_camera_world, float* d_projection,
-                            float* d_camera_centre, void* const* stage_events, void* stream) {
-  return gs_frame_bwd_part(f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection,
-                           workspace, workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth,
-                           grad_img_var, attached_points, attached_depth, d_position, d_log_scaling, d_rotation,
-                           d_alpha_logit, d_feature, d_T_camera_world, d_projection, d_camera_centre, stage_events,
-                           stream, nullptr);
+                            const float* grad_img_depth, const float* grad_img_var, const float* grad_weight,
+                            const float* attached_points, const float* attached_depth, float* d_position,
+                            float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                            float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                            void* const* stage_events, const GsFrameBwdPart* part, void* stream) {
+  return frame_bwd(false, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var, grad_weight,
+                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
+                   d_T_camera_world, d_projection, d_camera_centre, stage_events, part, stream);
+}
+
+extern "C" int gs_frame_bwd_rows(const GsFrame* f, const float* position, const float* log_scaling, const float* rotation,
+                                 const float* alpha_logit, const float* feature, const float* T_camera_world,
+                                 const float* projection, void* workspace, int64_t workspace_bytes, void* scratch,
+                                 int64_t scratch_bytes, int64_t v, int64_t k, const float* grad_image,
+                                 const float* grad_img_depth, const float* grad_img_var, const float* grad_weight,
+                                 const float* attached_points, const float* attached_depth, float* d_position,
+                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, float* d_feature,
+                                 float* d_T_camera_world, float* d_projection, float* d_camera_centre,
+                                 void* const* stage_events, const GsFrameBwdPart* part, void* stream) {
+  return frame_bwd(true, f, position, log_scaling, rotation, alpha_logit, feature, T_camera_world, projection, workspace,
+                   workspace_bytes, scratch, scratch_bytes, v, k, grad_image, grad_img_depth, grad_img_var, grad_weight,
+                   attached_points, attached_depth, d_position, d_log_scaling, d_rotation, d_alpha_logit, d_feature,
+                   d_T_camera_world, d_projection, d_camera_centre, stage_events, part, stream);
 }

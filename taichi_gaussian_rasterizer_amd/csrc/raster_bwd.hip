@@ -578,12 +578,12 @@ __global__ void unpack_kernel(int64_t v, int F, int row_floats, const float* row
 
 extern "C" int32_t gs_grad_row_floats(int32_t num_features) { return int32_t(gs_align_up(9 + num_features, 16)); }
 
-extern "C" int gs_raster_bwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                                const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                                int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
-                                const int32_t* heavy_tiles, const float* image, const float* grad_image,
-                                const float* alpha, const float* grad_weight, float* grad_rows,
-                                const GsRowShard* shard, void* stream) {
+extern "C" int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const float* features,
+                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
+                             const int32_t* heavy_tiles, const float* image, const float* grad_image,
+                             const float* alpha, const float* grad_weight, float* grad_rows, const GsRowShard* shard,
+                             void* stream) {
   if (int rc = gs_check_cfg(cfg)) return rc;
   GS_REQUIRE(!grad_weight || alpha, GS_ERR_INVALID_ARGUMENT,
              "gs_raster_bwd: grad_weight without the forward's alpha image");
@@ -625,15 +625,6 @@ extern "C" int gs_raster_bwd_bg(int64_t v, int32_t num_features, const float* po
   if (nb == 1) return mode == 2 ? launch_fp<1, 2>(a, s) : mode == 1 ? launch_fp<1, 1>(a, s) : launch_fp<1, 0>(a, s);
   if (nb == 2) return mode == 2 ? launch_fp<2, 2>(a, s) : mode == 1 ? launch_fp<2, 1>(a, s) : launch_fp<2, 0>(a, s);
   return mode == 2 ? launch_fp<4, 2>(a, s) : mode == 1 ? launch_fp<4, 1>(a, s) : launch_fp<4, 0>(a, s);
-}
-
-extern "C" int gs_raster_bwd(int64_t v, int32_t num_features, const float* points, const float* features,
-                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
-                             const int32_t* heavy_tiles, const float* image, const float* grad_image,
-                             float* grad_rows, const GsRowShard* shard, void* stream) {
-  return gs_raster_bwd_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                          tile_order, heavy_tiles, image, grad_image, nullptr, nullptr, grad_rows, shard, stream);
 }
 
 extern "C" int gs_raster_bwd_unpack(int64_t v, int32_t num_features, const float* grad_rows, float* grad_points,

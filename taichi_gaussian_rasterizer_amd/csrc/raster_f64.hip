@@ -455,11 +455,11 @@ extern "C" int64_t gs_raster_f64_scratch_bytes(int64_t v, int64_t k, int32_t num
   return records(k, num_features) + gs_f64_group_scratch_bytes(k, v, 4);
 }
 
-extern "C" int gs_raster_fwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
-                                    const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                    int32_t width, int32_t height, const GsRasterConfigF64* cfg, double* image,
-                                    double* alpha, double* visibility, const double* background,
-                                    int32_t background_offset, void* scratch, int64_t scratch_bytes, void* stream) {
+extern "C" int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
+                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, double* image,
+                                 double* alpha, double* visibility, const double* background,
+                                 int32_t background_offset, void* scratch, int64_t scratch_bytes, void* stream) {
   if (int rc = check_raster(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
                             image, alpha, scratch, scratch_bytes, "gs_raster_fwd_f64"))
     return rc;
@@ -494,12 +494,12 @@ extern "C" int gs_raster_fwd_f64_bg(int64_t v, int32_t num_features, const doubl
   return GS_OK;
 }
 
-extern "C" int gs_raster_bwd_f64_bg(int64_t v, int32_t num_features, const double* points, const double* features,
-                                    const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                    int32_t width, int32_t height, const GsRasterConfigF64* cfg, const double* image,
-                                    const double* grad_image, const double* alpha, const double* grad_weight,
-                                    double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
-                                    int64_t scratch_bytes, void* stream) {
+extern "C" int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
+                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
+                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, const double* image,
+                                 const double* grad_image, const double* alpha, const double* grad_weight,
+                                 double* grad_points, double* grad_features, double* point_heuristic, void* scratch,
+                                 int64_t scratch_bytes, void* stream) {
   if (int rc = check_raster(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
                             image, grad_image, scratch, scratch_bytes, "gs_raster_bwd_f64"))
     return rc;
@@ -533,23 +533,4 @@ extern "C" int gs_raster_bwd_f64_bg(int64_t v, int32_t num_features, const doubl
                      7, grad_features, num_features, cfg->compute_point_heuristic ? point_heuristic : nullptr);
   GS_CHECK_LAUNCH("gs_raster_bwd_f64/sum");
   return GS_OK;
-}
-
-extern "C" int gs_raster_fwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
-                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, double* image,
-                                 double* alpha, double* visibility, void* scratch, int64_t scratch_bytes,
-                                 void* stream) {
-  return gs_raster_fwd_f64_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                              image, alpha, visibility, nullptr, 0, scratch, scratch_bytes, stream);
-}
-
-extern "C" int gs_raster_bwd_f64(int64_t v, int32_t num_features, const double* points, const double* features,
-                                 const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                 int32_t width, int32_t height, const GsRasterConfigF64* cfg, const double* image,
-                                 const double* grad_image, double* grad_points, double* grad_features,
-                                 double* point_heuristic, void* scratch, int64_t scratch_bytes, void* stream) {
-  return gs_raster_bwd_f64_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                              image, grad_image, nullptr, nullptr, grad_points, grad_features, point_heuristic, scratch,
-                              scratch_bytes, stream);
 }

@@ -341,12 +341,12 @@ int launch_fp(const FwdArgs& a, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int gs_raster_fwd_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                                const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                                int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
-                                const int32_t* heavy_tiles, float* image, float* alpha, float* visibility,
-                                const GsRowShard* shard, const float* background, int32_t background_offset,
-                                void* stream) {
+extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* points, const float* features,
+                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
+                             const int32_t* heavy_tiles, float* image, float* alpha, float* visibility,
+                             const GsRowShard* shard, const float* background, int32_t background_offset,
+                             void* stream) {
   if (int rc = gs_check_cfg(cfg)) return rc;
   if (int rc = gs_check_background("gs_raster_fwd", cfg->use_alpha_blending, background != nullptr, background_offset,
                                    num_features))
@@ -397,13 +397,4 @@ extern "C" int gs_raster_fwd_bg(int64_t v, int32_t num_features, const float* po
                                                                                               : launch_fp<2, 0>(a, s);
   return mode == 3 ? launch_fp<4, 3>(a, s) : mode == 2 ? launch_fp<4, 2>(a, s) : mode == 1 ? launch_fp<4, 1>(a, s)
                                                                                             : launch_fp<4, 0>(a, s);
-}
-
-extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* points, const float* features,
-                             const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                             int32_t height, const GsRasterConfig* cfg, const int32_t* tile_order,
-                             const int32_t* heavy_tiles, float* image, float* alpha, float* visibility,
-                             const GsRowShard* shard, void* stream) {
-  return gs_raster_fwd_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                          tile_order, heavy_tiles, image, alpha, visibility, shard, nullptr, 0, stream);
 }

@@ -508,11 +508,11 @@ int wide_setup(const char* what, int32_t num_features, int32_t width, int32_t he
 
 }  // namespace
 
-extern "C" int gs_raster_fwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                     int32_t width, int32_t height, const GsRasterConfig* cfg, float* image,
-                                     float* alpha, float* visibility, const float* background,
-                                     int32_t background_offset, void* stream) {
+extern "C" int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
+                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                                  int32_t height, const GsRasterConfig* cfg, float* image, float* alpha,
+                                  float* visibility, const float* background, int32_t background_offset,
+                                  void* stream) {
   WideArgs a;
   if (int rc = wide_setup("gs_raster_fwd_wide", num_features, width, height, cfg, a)) return rc;
   if (int rc = gs_check_background("gs_raster_fwd_wide", cfg->use_alpha_blending, background != nullptr,
@@ -532,11 +532,11 @@ extern "C" int gs_raster_fwd_wide_bg(int64_t v, int32_t num_features, const floa
   return GS_OK;
 }
 
-extern "C" int gs_raster_bwd_wide_bg(int64_t v, int32_t num_features, const float* points, const float* features,
-                                     const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k,
-                                     int32_t width, int32_t height, const GsRasterConfig* cfg, const float* image,
-                                     const float* grad_image, const float* alpha, const float* grad_weight,
-                                     float* grad_points, float* grad_features, float* point_heuristic, void* stream) {
+extern "C" int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
+                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
+                                  int32_t height, const GsRasterConfig* cfg, const float* image,
+                                  const float* grad_image, const float* alpha, const float* grad_weight,
+                                  float* grad_points, float* grad_features, float* point_heuristic, void* stream) {
   WideArgs a;
   if (int rc = wide_setup("gs_raster_bwd_wide", num_features, width, height, cfg, a)) return rc;
   GS_REQUIRE(!grad_weight || alpha, GS_ERR_INVALID_ARGUMENT,
@@ -556,21 +556,4 @@ extern "C" int gs_raster_bwd_wide_bg(int64_t v, int32_t num_features, const floa
                      static_cast<hipStream_t>(stream), a);
   GS_CHECK_LAUNCH("gs_raster_bwd_wide");
   return GS_OK;
-}
-
-extern "C" int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
-                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                                  int32_t height, const GsRasterConfig* cfg, float* image, float* alpha,
-                                  float* visibility, void* stream) {
-  return gs_raster_fwd_wide_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                               image, alpha, visibility, nullptr, 0, stream);
-}
-
-extern "C" int gs_raster_bwd_wide(int64_t v, int32_t num_features, const float* points, const float* features,
-                                  const int32_t* tile_ranges, const int32_t* overlap_to_point, int64_t k, int32_t width,
-                                  int32_t height, const GsRasterConfig* cfg, const float* image,
-                                  const float* grad_image, float* grad_points, float* grad_features,
-                                  float* point_heuristic, void* stream) {
-  return gs_raster_bwd_wide_bg(v, num_features, points, features, tile_ranges, overlap_to_point, k, width, height, cfg,
-                               image, grad_image, nullptr, nullptr, grad_points, grad_features, point_heuristic, stream);
 }

@@ -193,11 +193,10 @@ def _forward_call(m, inputs, needs_grad, depth_range, use_depth16, render_median
     scratch = torch.empty((L.fwd_scratch_bytes,), dtype=torch.uint8, device=dev)
     host_counts = _pinned_counts(dev)
     ready, ready_handle = _counts_event(dev)
-    # background None: gs_frame_fwd itself (which is this call with NULL)
-    nv.check(lib.gs_frame_fwd_bg(ctypes.byref(frame), nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation),
-                                 nv.ptr(alpha_logit), nv.ptr(feature), nv.ptr(T), nv.ptr(proj), nv.ptr(ws),
-                                 L.workspace_bytes, nv.ptr(scratch), L.fwd_scratch_bytes, nv.ptr(host_counts),
-                                 ready_handle, nv.stage_events(nv.FRAME_FWD_STAGES), nv.ptr(background), nv.stream()),
+    nv.check(lib.gs_frame_fwd(ctypes.byref(frame), nv.ptr(position), nv.ptr(log_scaling), nv.ptr(rotation),
+                              nv.ptr(alpha_logit), nv.ptr(feature), nv.ptr(T), nv.ptr(proj), nv.ptr(ws),
+                              L.workspace_bytes, nv.ptr(scratch), L.fwd_scratch_bytes, nv.ptr(host_counts),
+                              ready_handle, nv.stage_events(nv.FRAME_FWD_STAGES), nv.ptr(background), nv.stream()),
              "gs_frame_fwd")
     ready.synchronize()  # waits for the mapper's scan only, not for the rasterizer
     host = host_counts.tolist()
@@ -395,8 +394,7 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha=N
     flat = torch.empty((at,), dtype=torch.float32, device=dev)
     outs = [flat.as_strided(t.shape if out_rows == n else (out_rows, *t.shape[1:]), t.stride(), start)
             for t, start in zip(params, starts)]
-    # grad_weight None: gs_frame_bwd_rows / gs_frame_bwd_part themselves (which are these calls with NULL)
-    frame_bwd = lib.gs_frame_bwd_rows_bg if compact else lib.gs_frame_bwd_part_bg
+    frame_bwd = lib.gs_frame_bwd_rows if compact else lib.gs_frame_bwd
     d_T = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_T else None
     d_proj = torch.empty((4,), dtype=torch.float32, device=dev) if need_proj else None
     d_centre = None
@@ -411,10 +409,9 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha=N
             0 if splats is None else splats.stride(0), lo, hi))
         nv.check(frame_bwd(ctypes.byref(frame), *map(nv.ptr, inputs), nv.ptr(ws), L.workspace_bytes,
                            nv.ptr(scratch), L.bwd_scratch_bytes, V, K, nv.ptr(gi), nv.ptr(gd_), nv.ptr(gv_),
-                           nv.ptr(att_p), nv.ptr(att_d), *map(nv.ptr, outs), nv.ptr(d_T), nv.ptr(d_proj),
-                           nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), nv.stream(), part,
-                           nv.ptr(gw)),
-                 "gs_frame_bwd_rows" if compact else "gs_frame_bwd_part")
+                           nv.ptr(gw), nv.ptr(att_p), nv.ptr(att_d), *map(nv.ptr, outs), nv.ptr(d_T), nv.ptr(d_proj),
+                           nv.ptr(d_centre), nv.stage_events(nv.FRAME_BWD_STAGES, stages), part, nv.stream()),
+                 "gs_frame_bwd_rows" if compact else "gs_frame_bwd")
 
     call(None if whole else range(nv.GS_BWD_RASTER, nv.GS_BWD_COLOURS))
     if m["config"].compute_point_heuristic and V > 0:

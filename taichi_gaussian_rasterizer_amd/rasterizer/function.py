@@ -58,15 +58,15 @@ class _RasterFunction(torch.autograd.Function):
         vis = (torch.zeros((v,), dtype=torch.float32, device=dev) if want_vis
                else torch.empty((0,), dtype=torch.float32, device=dev))
         if F <= MAX_FEATURES:
-            nv.check(lib.gs_raster_fwd_bg(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
-                                          nv.make_config(config), None, None, nv.ptr(image), nv.ptr(alpha),
-                                          nv.ptr(vis) if want_vis else None, None, nv.ptr(bg), ctx.background_offset,
-                                          nv.stream()), "gs_raster_fwd")
+            nv.check(lib.gs_raster_fwd(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                       nv.make_config(config), None, None, nv.ptr(image), nv.ptr(alpha),
+                                       nv.ptr(vis) if want_vis else None, None, nv.ptr(bg), ctx.background_offset,
+                                       nv.stream()), "gs_raster_fwd")
         else:
-            nv.check(lib.gs_raster_fwd_wide_bg(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0],
-                                               w, h, nv.make_config(config), nv.ptr(image), nv.ptr(alpha),
-                                               nv.ptr(vis) if want_vis else None, nv.ptr(bg), ctx.background_offset,
-                                               nv.stream()), "gs_raster_fwd_wide")
+            nv.check(lib.gs_raster_fwd_wide(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0],
+                                            w, h, nv.make_config(config), nv.ptr(image), nv.ptr(alpha),
+                                            nv.ptr(vis) if want_vis else None, nv.ptr(bg), ctx.background_offset,
+                                            nv.stream()), "gs_raster_fwd_wide")
         if not config.compute_visibility:
             vis_out = torch.empty((0,), dtype=torch.float32, device=dev) if not want_vis else vis
         else:
@@ -93,17 +93,17 @@ class _RasterFunction(torch.autograd.Function):
             grad_g = torch.zeros_like(g)
             grad_f = torch.zeros_like(f)
             heur = ctx.heur if config.compute_point_heuristic else None
-            nv.check(lib.gs_raster_bwd_wide_bg(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0],
-                                               w, h, nv.make_config(config), nv.ptr(image), nv.ptr(gi),
-                                               nv.ptr(alpha) if gw is not None else None, nv.ptr(gw), nv.ptr(grad_g),
-                                               nv.ptr(grad_f), nv.ptr(heur), nv.stream()), "gs_raster_bwd_wide")
+            nv.check(lib.gs_raster_bwd_wide(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0],
+                                            w, h, nv.make_config(config), nv.ptr(image), nv.ptr(gi),
+                                            nv.ptr(alpha) if gw is not None else None, nv.ptr(gw), nv.ptr(grad_g),
+                                            nv.ptr(grad_f), nv.ptr(heur), nv.stream()), "gs_raster_bwd_wide")
             return (grad_g, grad_f, None, None, None, None, *tail)
         row = lib.gs_grad_row_floats(F)
         rows = torch.zeros((v, row), dtype=torch.float32, device=g.device)
-        nv.check(lib.gs_raster_bwd_bg(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
-                                      nv.make_config(config), None, None, nv.ptr(image), nv.ptr(gi),
-                                      nv.ptr(alpha) if gw is not None else None, nv.ptr(gw), nv.ptr(rows), None,
-                                      nv.stream()), "gs_raster_bwd")
+        nv.check(lib.gs_raster_bwd(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                   nv.make_config(config), None, None, nv.ptr(image), nv.ptr(gi),
+                                   nv.ptr(alpha) if gw is not None else None, nv.ptr(gw), nv.ptr(rows), None,
+                                   nv.stream()), "gs_raster_bwd")
         grad_g = torch.empty_like(g)
         grad_f = torch.empty_like(f)
         heur = ctx.heur if config.compute_point_heuristic else None
@@ -155,10 +155,10 @@ def _forward_f64(ctx, gaussians, features, overlap_to_point, tile_overlap_ranges
     vis = torch.zeros((v if want_vis else 0,), dtype=torch.float64, device=dev)
     nbytes = lib.gs_raster_f64_scratch_bytes(v, o2p.shape[0], F)
     scratch = nv.scratch(nbytes, dev)
-    nv.check(lib.gs_raster_fwd_f64_bg(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
-                                      nv.make_config_f64(config), nv.ptr(image), nv.ptr(alpha),
-                                      nv.ptr(vis) if want_vis else None, nv.ptr(ctx.background), ctx.background_offset,
-                                      nv.ptr(scratch), nbytes, nv.stream()), "gs_raster_fwd_f64")
+    nv.check(lib.gs_raster_fwd_f64(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                   nv.make_config_f64(config), nv.ptr(image), nv.ptr(alpha),
+                                   nv.ptr(vis) if want_vis else None, nv.ptr(ctx.background), ctx.background_offset,
+                                   nv.ptr(scratch), nbytes, nv.stream()), "gs_raster_fwd_f64")
     vis_out = vis if config.compute_visibility else torch.empty((0,), dtype=torch.float64, device=dev)
     ctx.image_size, ctx.config = (w, h), config
     ctx.heur = heur
@@ -181,11 +181,11 @@ def _backward_f64(ctx, grad_image, grad_alpha):
     grad_f = torch.empty_like(f)
     nbytes = lib.gs_raster_f64_scratch_bytes(v, o2p.shape[0], F)
     scratch = nv.scratch(nbytes, g.device)
-    nv.check(lib.gs_raster_bwd_f64_bg(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
-                                      nv.make_config_f64(config), nv.ptr(image), nv.ptr(gi),
-                                      nv.ptr(alpha) if gw is not None else None, nv.ptr(gw), nv.ptr(grad_g),
-                                      nv.ptr(grad_f), nv.ptr(ctx.heur) if config.compute_point_heuristic else None,
-                                      nv.ptr(scratch), nbytes, nv.stream()), "gs_raster_bwd_f64")
+    nv.check(lib.gs_raster_bwd_f64(v, F, nv.ptr(g), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), o2p.shape[0], w, h,
+                                   nv.make_config_f64(config), nv.ptr(image), nv.ptr(gi),
+                                   nv.ptr(alpha) if gw is not None else None, nv.ptr(gw), nv.ptr(grad_g),
+                                   nv.ptr(grad_f), nv.ptr(ctx.heur) if config.compute_point_heuristic else None,
+                                   nv.ptr(scratch), nbytes, nv.stream()), "gs_raster_bwd_f64")
     return grad_g, grad_f, None, None, None, None, _background_grad(ctx, gi, alpha), None, None
 
 

