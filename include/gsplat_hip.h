@@ -568,8 +568,9 @@ int gs_optim_step_rows(int32_t laprop, int32_t vector_group, int64_t rows, int32
 
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
- * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  They restate the
- * reference formulas literally with IEEE sqrt / exp / log; none of the f32 kernels' reformulations.  Every result is
+ * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are
+ * the f32 kernels' arithmetic instantiated with double and IEEE sqrt / exp / log; the rasterizer states the reference
+ * formulas literally, with none of the f32 kernels' reformulations.  Every result is
  * bit-reproducible: no float atomic feeds an output (per-entry records summed in a fixed order).  Scope: no tile
  * order, heavy-tile split, row shard or stride options; features up to GS_MAX_FEATURES; forward_cut does not exist
  * here (the forward blends a tile's whole list, as the reference does). */

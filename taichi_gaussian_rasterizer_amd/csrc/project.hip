@@ -108,131 +108,7 @@ __global__ __launch_bounds__(256) void compact_kernel(int64_t n, const float4* s
 }
 
 // ------------------------------------------------------------------------------- backward
-struct BwdArgs {
-  ProjArgs f;
-  const int* slot_of;
-  const float* gpoints;  // row stride gpoints_stride, or null
-  const float* gdepth;   // stride gdepth_stride, or null
-  const float* gdepth_sq;  // optional gradient of a z^2 feature (adds 2 z g), same stride as gdepth
-  int gpoints_stride, gdepth_stride;
-  float* d_position;
-  float* d_log_scaling;
-  float* d_rotation;
-  float* d_alpha_logit;
-  float* cam_partials;  // (num_blocks,16) or null
-};
-
-// The adjoint of one visible Gaussian: i = its row in the parameter tensors, slot = its row in the upstream gradients.
-// Shared by the dense kernel (one lane per Gaussian) and the row-compact one (one lane per visible row), so that a
-// visible row's four gradients are the same bits either way.
-template <bool CAMERA>
-__device__ __forceinline__ void project_bwd_row(const BwdArgs& a, const int64_t i, const int slot, float (&dpos)[3],
-                                                float (&dls)[3], float (&dq)[4], float& dal, float (&gcam_acc)[16]) {
-  const Cam c = load_cam(a.f.T44, a.f.proj);
-  Fwd f;
-  forward(a.f, c, i, f);
-  float g[7] = {0, 0, 0, 0, 0, 0, 0}, gz = 0.0f;
-  if (a.gpoints) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) g[k] = a.gpoints[int64_t(slot) * a.gpoints_stride + k];
-  }
-  if (a.gdepth) gz = a.gdepth[int64_t(slot) * a.gdepth_stride];
-  if (a.gdepth_sq) gz += 2.0f * f.cam[2] * a.gdepth_sq[int64_t(slot) * a.gdepth_stride];
-  // alpha = sigmoid(logit)
-  dal = g[6] * f.alpha * (1.0f - f.alpha);
-  // sigma = sqrt(lambda)
-  float gl1 = g[4] * 0.5f / f.s1, gl2 = g[5] * 0.5f / f.s2;
-  // axis = v / |v|
-  const float dotag = f.ax * g[2] + f.ay * g[3];
-  const float gvx = (g[2] - f.ax * dotag) / f.vn, gvy = (g[3] - f.ay * dotag) / f.vn;
-  float gc00 = gvx, gc01 = gvy, gc11 = 0.0f;
-  gl2 -= gvx;
-  // lambda1,2 = (tr +- sg)/2
-  float gtr = 0.5f * (gl1 + gl2);
-  const float gsg = 0.5f * (gl1 - gl2);
-  // sg = sqrt(max(gap,0)); at gap == 0 the reference's autodiff yields inf/NaN, we return 0
-  const float ggap = (f.gap > 0.0f && f.sg > 0.0f) ? gsg * 0.5f / f.sg : 0.0f;
-  gtr += 2.0f * f.tr * ggap;
-  const float gdet = -4.0f * ggap;
-  gc00 += gdet * f.c11 + gtr;
-  gc11 += gdet * f.c00 + gtr;
-  gc01 += -2.0f * f.c01 * gdet;
-  // cov = m m^T
-  float gN[2][3], gs[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float gm0 = 2.0f * gc00 * f.m[0][k] + gc01 * f.m[1][k];
-    const float gm1 = 2.0f * gc11 * f.m[1][k] + gc01 * f.m[0][k];
-    gs[k] = gm0 * f.N[0][k] + gm1 * f.N[1][k];
-    gN[0][k] = gm0 * f.s[k];
-    gN[1][k] = gm1 * f.s[k];
-    dls[k] = gs[k] * f.s[k];  // s = exp(log_scale)
-  }
-  // N = J M3
-  float gJ00 = 0, gJ02 = 0, gJ11 = 0, gJ12 = 0, gM3[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    gJ00 += gN[0][k] * f.M3[0][k];
-    gJ02 += gN[0][k] * f.M3[2][k];
-    gJ11 += gN[1][k] * f.M3[1][k];
-    gJ12 += gN[1][k] * f.M3[2][k];
-    gM3[0][k] = f.J00 * gN[0][k];
-    gM3[1][k] = f.J11 * gN[1][k];
-    gM3[2][k] = f.J02 * gN[0][k] + f.J12 * gN[1][k];
-  }
-  // M3 = Tr R :  gR = Tr^T gM3 ; gTr = gM3 R^T
-  float gR[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      gR[r][k] = c.T[0 * 4 + r] * gM3[0][k] + c.T[1 * 4 + r] * gM3[1][k] + c.T[2 * 4 + r] * gM3[2][k];
-      if (CAMERA) gcam_acc[r * 4 + k] += gM3[r][0] * f.R[k][0] + gM3[r][1] * f.R[k][1] + gM3[r][2] * f.R[k][2];
-    }
-  // R = quat_to_mat(qn)  (generic.py:407-416)
-  const float x = f.qn[0], y = f.qn[1], z = f.qn[2], w = f.qn[3];
-  float gq[4];
-  gq[0] = 2.0f * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2.0f * x * gR[1][1] - w * gR[1][2] + z * gR[2][0] +
-                  w * gR[2][1] - 2.0f * x * gR[2][2]);
-  gq[1] = 2.0f * (-2.0f * y * gR[0][0] + x * gR[0][1] + w * gR[0][2] + x * gR[1][0] + z * gR[1][2] - w * gR[2][0] +
-                  z * gR[2][1] - 2.0f * y * gR[2][2]);
-  gq[2] = 2.0f * (-2.0f * z * gR[0][0] - w * gR[0][1] + x * gR[0][2] + w * gR[1][0] - 2.0f * z * gR[1][1] +
-                  y * gR[1][2] + x * gR[2][0] + y * gR[2][1]);
-  gq[3] = 2.0f * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
-  // qn = q / |q|
-  const float dotq = f.qn[0] * gq[0] + f.qn[1] * gq[1] + f.qn[2] * gq[2] + f.qn[3] * gq[3];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) dq[k] = (gq[k] - f.qn[k] * dotq) / f.qlen;
-  // J and the projected mean
-  const float zc = f.cam[2], iz = 1.0f / zc;
-  float gzc = gz;
-  float gfx = gJ00 * iz, gfy = gJ11 * iz;
-  gzc += -gJ00 * c.fx * iz * iz - gJ11 * c.fy * iz * iz;
-  gzc += gJ02 * (f.tx - c.cx) * iz * iz + gJ12 * (f.ty - c.cy) * iz * iz;
-  float gcx = gJ02 * iz, gcy = gJ12 * iz;
-  const float gu = g[0] + (f.in_x ? -gJ02 * iz : 0.0f);  // clamp: zero gradient outside the margin
-  const float gv = g[1] + (f.in_y ? -gJ12 * iz : 0.0f);
-  gfx += gu * f.cam[0] * iz;
-  gfy += gv * f.cam[1] * iz;
-  gcx += gu; gcy += gv;
-  const float gcamx = gu * c.fx * iz, gcamy = gv * c.fy * iz;
-  gzc += -gu * c.fx * f.cam[0] * iz * iz - gv * c.fy * f.cam[1] * iz * iz;
-  // cam = Tr p + t
-  const float gcamv[3] = {gcamx, gcamy, gzc};
-  const float px = a.f.position[3 * i], py = a.f.position[3 * i + 1], pz = a.f.position[3 * i + 2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) dpos[k] = c.T[0 * 4 + k] * gcamv[0] + c.T[1 * 4 + k] * gcamv[1] + c.T[2 * 4 + k] * gcamv[2];
-  if (CAMERA) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      gcam_acc[r * 4 + 0] += gcamv[r] * px;
-      gcam_acc[r * 4 + 1] += gcamv[r] * py;
-      gcam_acc[r * 4 + 2] += gcamv[r] * pz;
-      gcam_acc[r * 4 + 3] += gcamv[r];
-    }
-    gcam_acc[12] = gfx; gcam_acc[13] = gfy; gcam_acc[14] = gcx; gcam_acc[15] = gcy;
-  }
-}
+// (BwdArgs and the adjoint of one visible Gaussian, project_bwd_row: project_math.h)
 
 // One lane of the adjoint, whole: Gaussian i (if `valid`), upstream gradients in row `slot` (< 0: culled, zeros), the
 // four gradients to row `out`; then the block's camera partials.  The dense and the row-compact kernel differ only in
@@ -246,7 +122,7 @@ __device__ __forceinline__ void project_bwd_lane(const BwdArgs& a, const bool va
   if (valid) {
     float dpos[3] = {0, 0, 0}, dls[3] = {0, 0, 0}, dq[4] = {0, 0, 0, 0}, dal = 0;
     if (slot >= 0) {
-      project_bwd_row<CAMERA>(a, i, slot, dpos, dls, dq, dal, gcam_acc);
+      project_bwd_row<float, CAMERA>(a, i, slot, dpos, dls, dq, dal, gcam_acc);
     }
 #pragma unroll
     // gradients are written once and read by the optimizer later: keep them out of the caches the next frame's

@@ -8,56 +8,12 @@
 // coefficient row (192 B at degree 3, C = 3) is read with 16-byte loads when its size allows.
 
 #include "gs_common.h"
+#include "sh_math.h"
 
 namespace {
 
-constexpr float C1 = 0.48860251190292f, C2 = 1.09254843059208f, C3 = 0.94617469575756f, C4 = 0.31539156525252f,
-                C5 = 0.54627421529604f, C6 = 0.590043589926644f, C7 = 2.89061144264055f, C8 = 0.304697199642977f,
-                C9 = 1.24392110863372f, C10 = 0.497568443453487f, C11 = 1.44530572132028f;
-
-template <int DEG>
-__device__ __forceinline__ void rsh(float x, float y, float z, float* Y) {
-  Y[0] = 0.282094791773878f;
-  if (DEG >= 1) { Y[1] = -C1 * y; Y[2] = C1 * z; Y[3] = -C1 * x; }
-  if (DEG >= 2) {
-    Y[4] = C2 * (x * y); Y[5] = -C2 * (y * z); Y[6] = C3 * (z * z) - C4; Y[7] = -C2 * (x * z);
-    Y[8] = C5 * (x * x) - C5 * (y * y);
-  }
-  if (DEG >= 3) {
-    const float x2 = x * x, y2 = y * y, z2 = z * z;
-    Y[9] = -C6 * y * (3.0f * x2 - y2);
-    Y[10] = C7 * (x * y) * z;
-    Y[11] = C8 * y * (1.5f - 7.5f * z2);
-    Y[12] = C9 * z * (1.5f * z2 - 0.5f) - C10 * z;
-    Y[13] = C8 * x * (1.5f - 7.5f * z2);
-    Y[14] = C11 * z * (x2 - y2);
-    Y[15] = -C6 * x * (x2 - 3.0f * y2);
-  }
-}
-
-// g_dir = sum_d w[d] * dY_d/d(x,y,z)
-template <int DEG>
-__device__ __forceinline__ void rsh_grad(float x, float y, float z, const float* w, float* g) {
-  g[0] = g[1] = g[2] = 0.0f;
-  if (DEG >= 1) { g[1] += -C1 * w[1]; g[2] += C1 * w[2]; g[0] += -C1 * w[3]; }
-  if (DEG >= 2) {
-    g[0] += C2 * y * w[4];            g[1] += C2 * x * w[4];
-    g[1] += -C2 * z * w[5];           g[2] += -C2 * y * w[5];
-    g[2] += 2.0f * C3 * z * w[6];
-    g[0] += -C2 * z * w[7];           g[2] += -C2 * x * w[7];
-    g[0] += 2.0f * C5 * x * w[8];     g[1] += -2.0f * C5 * y * w[8];
-  }
-  if (DEG >= 3) {
-    const float x2 = x * x, y2 = y * y, z2 = z * z;
-    g[0] += -6.0f * C6 * x * y * w[9];          g[1] += -C6 * (3.0f * x2 - 3.0f * y2) * w[9];
-    g[0] += C7 * y * z * w[10];                 g[1] += C7 * x * z * w[10];            g[2] += C7 * x * y * w[10];
-    g[1] += C8 * (1.5f - 7.5f * z2) * w[11];    g[2] += -15.0f * C8 * y * z * w[11];
-    g[2] += (C9 * (4.5f * z2 - 0.5f) - C10) * w[12];
-    g[0] += C8 * (1.5f - 7.5f * z2) * w[13];    g[2] += -15.0f * C8 * x * z * w[13];
-    g[0] += 2.0f * C11 * x * z * w[14];         g[1] += -2.0f * C11 * y * z * w[14];   g[2] += C11 * (x2 - y2) * w[14];
-    g[0] += -C6 * (3.0f * x2 - 3.0f * y2) * w[15];  g[1] += 6.0f * C6 * x * y * w[15];
-  }
-}
+using gs_sh::rsh;
+using gs_sh::rsh_grad;
 
 template <int D>
 __device__ __forceinline__ void load_row(const float* row, float* out) {
@@ -130,7 +86,7 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(int64_t v, const int* v_dev
     const float dx = positions[3 * idx] - cam[0], dy = positions[3 * idx + 1] - cam[1], dz = positions[3 * idx + 2] - cam[2];
     const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
     float Y[D];
-    rsh<DEG>(dx / nrm, dy / nrm, dz / nrm, Y);
+    rsh<float, DEG>(dx / nrm, dy / nrm, dz / nrm, Y);
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       float acc = 0.0f;
@@ -143,7 +99,7 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(int64_t v, const int* v_dev
   const float dx = positions[3 * idx] - cam[0], dy = positions[3 * idx + 1] - cam[1], dz = positions[3 * idx + 2] - cam[2];
   const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
   float Y[D];
-  rsh<DEG>(dx / nrm, dy / nrm, dz / nrm, Y);
+  rsh<float, DEG>(dx / nrm, dy / nrm, dz / nrm, Y);
   for (int c = 0; c < C; ++c) {
     float row[D];
     load_row<D>(params + (idx * C + c) * D, row);
@@ -173,7 +129,7 @@ __global__ __launch_bounds__(256) void sh_bwd_kernel(int64_t v, int C, const flo
     const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
     const float x = dx / nrm, y = dy / nrm, z = dz / nrm;
     float Y[D], w[D];
-    rsh<DEG>(x, y, z, Y);
+    rsh<float, DEG>(x, y, z, Y);
 #pragma unroll
     for (int d = 0; d < D; ++d) w[d] = 0.0f;
     for (int c = 0; c < C; ++c) {
@@ -194,7 +150,7 @@ __global__ __launch_bounds__(256) void sh_bwd_kernel(int64_t v, int C, const flo
     }
     if (DEG >= 1 && (d_positions || d_cam)) {
       float gdir[3];
-      rsh_grad<DEG>(x, y, z, w, gdir);
+      rsh_grad<float, DEG>(x, y, z, w, gdir);
       const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
       gd[0] = (gdir[0] - x * dot) / nrm;
       gd[1] = (gdir[1] - y * dot) / nrm;
@@ -259,7 +215,7 @@ __global__ __launch_bounds__(256) void sh_bwd_dense_kernel(int64_t n, int C, con
       const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
       const float x = dx / nrm, y = dy / nrm, z = dz / nrm;
       float Y[D], w[D];
-      rsh<DEG>(x, y, z, Y);
+      rsh<float, DEG>(x, y, z, Y);
 #pragma unroll
       for (int d = 0; d < D; ++d) w[d] = 0.0f;
       const bool need_dir = d_positions != nullptr || d_cam != nullptr;
@@ -302,7 +258,7 @@ __global__ __launch_bounds__(256) void sh_bwd_dense_kernel(int64_t n, int C, con
       }
       if (DEG >= 1 && (d_positions || d_cam)) {
         float gdir[3];
-        rsh_grad<DEG>(x, y, z, w, gdir);
+        rsh_grad<float, DEG>(x, y, z, w, gdir);
         const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
         gd[0] = (gdir[0] - x * dot) / nrm;
         gd[1] = (gdir[1] - y * dot) / nrm;
@@ -367,7 +323,7 @@ __global__ __launch_bounds__(256) void sh_bwd_rows_kernel(int64_t v, int C, cons
     const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
     const float x = dx / nrm, y = dy / nrm, z = dz / nrm;
     float Y[D], w[D];
-    rsh<DEG>(x, y, z, Y);
+    rsh<float, DEG>(x, y, z, Y);
 #pragma unroll
     for (int d = 0; d < D; ++d) w[d] = 0.0f;
     const bool need_dir = d_positions != nullptr || d_cam != nullptr;
@@ -409,7 +365,7 @@ __global__ __launch_bounds__(256) void sh_bwd_rows_kernel(int64_t v, int C, cons
     }
     if (DEG >= 1 && (d_positions || d_cam)) {
       float gdir[3];
-      rsh_grad<DEG>(x, y, z, w, gdir);
+      rsh_grad<float, DEG>(x, y, z, w, gdir);
       const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
       gd[0] = (gdir[0] - x * dot) / nrm;
       gd[1] = (gdir[1] - y * dot) / nrm;

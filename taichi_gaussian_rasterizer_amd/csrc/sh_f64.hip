@@ -1,5 +1,6 @@
 // sh_f64.hip -- view-dependent colour from real spherical harmonics in float64, and its adjoint, for gradcheck.
-// sh.hip's formulas (spherical_harmonics.py:38-106, :118-134) with double constants.  out[c] = clamp(sum_d Y_d(dir) *
+// The harmonics and their gradient are the functions sh.hip compiles (sh_math.h, spherical_harmonics.py:38-106),
+// instantiated with double; the kernels around them are this file's own (:118-134).  out[c] = clamp(sum_d Y_d(dir) *
 // sh[idx,c,d] + 0.5, 0, 1), dir = normalize(p[idx] - camera).
 //
 // The backward allows repeated indexes without float atomics: the list entries are grouped by Gaussian
@@ -7,66 +8,25 @@
 // Every entry of a Gaussian sees the same direction and the same clamp mask, so the lane needs only the sums.
 
 #include "f64_common.h"
+#include "sh_math.h"
 
 namespace {
 
-constexpr double C0 = 0.282094791773878, C1 = 0.48860251190292, C2 = 1.09254843059208, C3 = 0.94617469575756,
-                 C4 = 0.31539156525252, C5 = 0.54627421529604, C6 = 0.590043589926644, C7 = 2.89061144264055,
-                 C8 = 0.304697199642977, C9 = 1.24392110863372, C10 = 0.497568443453487, C11 = 1.44530572132028;
+using gs_sh::rsh;
+using gs_sh::rsh_grad;
 
-__device__ __forceinline__ void rsh(int deg, double x, double y, double z, double* Y) {
-  Y[0] = C0;
-  if (deg >= 1) { Y[1] = -C1 * y; Y[2] = C1 * z; Y[3] = -C1 * x; }
-  if (deg >= 2) {
-    Y[4] = C2 * (x * y); Y[5] = -C2 * (y * z); Y[6] = C3 * (z * z) - C4; Y[7] = -C2 * (x * z);
-    Y[8] = C5 * (x * x) - C5 * (y * y);
-  }
-  if (deg >= 3) {
-    const double x2 = x * x, y2 = y * y, z2 = z * z;
-    Y[9] = -C6 * y * (3.0 * x2 - y2);
-    Y[10] = C7 * (x * y) * z;
-    Y[11] = C8 * y * (1.5 - 7.5 * z2);
-    Y[12] = C9 * z * (1.5 * z2 - 0.5) - C10 * z;
-    Y[13] = C8 * x * (1.5 - 7.5 * z2);
-    Y[14] = C11 * z * (x2 - y2);
-    Y[15] = -C6 * x * (x2 - 3.0 * y2);
-  }
-}
-
-// g = sum_d w[d] * dY_d/d(x,y,z)
-__device__ __forceinline__ void rsh_grad(int deg, double x, double y, double z, const double* w, double* g) {
-  g[0] = g[1] = g[2] = 0.0;
-  if (deg >= 1) { g[1] += -C1 * w[1]; g[2] += C1 * w[2]; g[0] += -C1 * w[3]; }
-  if (deg >= 2) {
-    g[0] += C2 * y * w[4];            g[1] += C2 * x * w[4];
-    g[1] += -C2 * z * w[5];           g[2] += -C2 * y * w[5];
-    g[2] += 2.0 * C3 * z * w[6];
-    g[0] += -C2 * z * w[7];           g[2] += -C2 * x * w[7];
-    g[0] += 2.0 * C5 * x * w[8];      g[1] += -2.0 * C5 * y * w[8];
-  }
-  if (deg >= 3) {
-    const double x2 = x * x, y2 = y * y, z2 = z * z;
-    g[0] += -6.0 * C6 * x * y * w[9];          g[1] += -C6 * (3.0 * x2 - 3.0 * y2) * w[9];
-    g[0] += C7 * y * z * w[10];                g[1] += C7 * x * z * w[10];            g[2] += C7 * x * y * w[10];
-    g[1] += C8 * (1.5 - 7.5 * z2) * w[11];     g[2] += -15.0 * C8 * y * z * w[11];
-    g[2] += (C9 * (4.5 * z2 - 0.5) - C10) * w[12];
-    g[0] += C8 * (1.5 - 7.5 * z2) * w[13];     g[2] += -15.0 * C8 * x * z * w[13];
-    g[0] += 2.0 * C11 * x * z * w[14];         g[1] += -2.0 * C11 * y * z * w[14];    g[2] += C11 * (x2 - y2) * w[14];
-    g[0] += -C6 * (3.0 * x2 - 3.0 * y2) * w[15];  g[1] += 6.0 * C6 * x * y * w[15];
-  }
-}
-
-__global__ __launch_bounds__(256) void sh_fwd_f64_kernel(int64_t v, int C, int deg, const double* params,
+template <int DEG>
+__global__ __launch_bounds__(256) void sh_fwd_f64_kernel(int64_t v, int C, const double* params,
                                                          const double* positions, const int64_t* indexes,
                                                          const double* cam, double* out) {
   const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (i >= v) return;
   const int64_t idx = indexes[i];
-  const int D = (deg + 1) * (deg + 1);
+  constexpr int D = (DEG + 1) * (DEG + 1);
   const double dx = positions[3 * idx] - cam[0], dy = positions[3 * idx + 1] - cam[1], dz = positions[3 * idx + 2] - cam[2];
   const double nrm = sqrt(dx * dx + dy * dy + dz * dz);
-  double Y[16];
-  rsh(deg, dx / nrm, dy / nrm, dz / nrm, Y);
+  double Y[D];
+  rsh<double, DEG>(dx / nrm, dy / nrm, dz / nrm, Y);
   for (int c = 0; c < C; ++c) {
     const double* row = params + (idx * C + c) * D;
     double acc = 0.0;
@@ -77,13 +37,14 @@ __global__ __launch_bounds__(256) void sh_fwd_f64_kernel(int64_t v, int C, int d
 }
 
 // one lane per Gaussian: its entries order[seg[2 j] .. seg[2 j + 1]) in ascending list order
-__global__ __launch_bounds__(256) void sh_bwd_f64_kernel(int64_t n, int C, int deg, const double* params,
+template <int DEG>
+__global__ __launch_bounds__(256) void sh_bwd_f64_kernel(int64_t n, int C, const double* params,
                                                          const double* positions, const int32_t* order,
                                                          const int32_t* seg, const double* cam, const double* gout,
                                                          double* d_params, double* d_positions, double* cam_partials) {
   __shared__ double s_red[4];
   const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  const int D = (deg + 1) * (deg + 1);
+  constexpr int D = (DEG + 1) * (DEG + 1);
   double gd[3] = {0, 0, 0};
   if (j < n) {
     const int e0 = seg[2 * j], e1 = seg[2 * j + 1];
@@ -93,8 +54,8 @@ __global__ __launch_bounds__(256) void sh_bwd_f64_kernel(int64_t n, int C, int d
       const double dx = positions[3 * j] - cam[0], dy = positions[3 * j + 1] - cam[1], dz = positions[3 * j + 2] - cam[2];
       const double nrm = sqrt(dx * dx + dy * dy + dz * dz);
       const double x = dx / nrm, y = dy / nrm, z = dz / nrm;
-      double Y[16], w[16];
-      rsh(deg, x, y, z, Y);
+      double Y[D], w[D];
+      rsh<double, DEG>(x, y, z, Y);
       for (int d = 0; d < D; ++d) w[d] = 0.0;
       for (int c = 0; c < C; ++c) {
         const double* row = params + (j * C + c) * D;
@@ -109,9 +70,9 @@ __global__ __launch_bounds__(256) void sh_bwd_f64_kernel(int64_t n, int C, int d
           w[d] += g * row[d];
         }
       }
-      if (deg >= 1) {
+      if (DEG >= 1) {
         double gdir[3];
-        rsh_grad(deg, x, y, z, w, gdir);
+        rsh_grad<double, DEG>(x, y, z, w, gdir);
         const double dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
         gd[0] = (gdir[0] - x * dot) / nrm;
         gd[1] = (gdir[1] - y * dot) / nrm;
@@ -156,8 +117,15 @@ extern "C" int gs_sh_fwd_f64(int64_t v, int32_t channels, int32_t degree, const 
   if (int rc = check_sh(0, v, channels, degree, "gs_sh_fwd_f64")) return rc;
   if (v == 0) return GS_OK;
   GS_REQUIRE(params && positions && indexes && camera_pos && out, GS_ERR_INVALID_ARGUMENT, "gs_sh_fwd_f64: NULL buffer");
-  hipLaunchKernelGGL(sh_fwd_f64_kernel, dim3(gs_div_up(v, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
-                     channels, degree, params, positions, indexes, camera_pos, out);
+#define SH_FWD_F64(DEG)                                                                                              \
+  hipLaunchKernelGGL(sh_fwd_f64_kernel<DEG>, dim3(gs_div_up(v, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), \
+                     v, channels, params, positions, indexes, camera_pos, out)
+  switch (degree) {
+    case 0: SH_FWD_F64(0); break;
+    case 1: SH_FWD_F64(1); break;
+    case 2: SH_FWD_F64(2); break;
+    default: SH_FWD_F64(3); break;
+  }
   GS_CHECK_LAUNCH("gs_sh_fwd_f64");
   return GS_OK;
 }
@@ -187,8 +155,15 @@ extern "C" int gs_sh_bwd_f64(int64_t n, int64_t v, int32_t channels, int32_t deg
   int32_t *order, *seg;
   if (int rc = gs_f64_group(v, 8, indexes, n, &order, &seg, static_cast<char*>(scratch) + pb, scratch_bytes - pb, s))
     return rc;
-  hipLaunchKernelGGL(sh_bwd_f64_kernel, dim3(nb), dim3(256), 0, s, n, channels, degree, params, positions, order, seg,
-                     camera_pos, grad_out, d_params, d_positions, d_camera_pos ? partials : nullptr);
+#define SH_BWD_F64(DEG)                                                                                             \
+  hipLaunchKernelGGL(sh_bwd_f64_kernel<DEG>, dim3(nb), dim3(256), 0, s, n, channels, params, positions, order, seg, \
+                     camera_pos, grad_out, d_params, d_positions, d_camera_pos ? partials : nullptr)
+  switch (degree) {
+    case 0: SH_BWD_F64(0); break;
+    case 1: SH_BWD_F64(1); break;
+    case 2: SH_BWD_F64(2); break;
+    default: SH_BWD_F64(3); break;
+  }
   GS_CHECK_LAUNCH("gs_sh_bwd_f64");
   if (d_camera_pos) {
     hipLaunchKernelGGL(sh_cam_reduce_f64_kernel, dim3(1), dim3(256), 0, s, nb, partials, d_camera_pos);

@@ -122,6 +122,50 @@ def test_projection_gradcheck(seed):
     assert gradcheck(fn, inputs, **GRADCHECK)
 
 
+def clamp_and_cull_scene():
+    """Six hand-placed Gaussians, image 40x24, for the branches the f32 and f64 adjoint share: camera at the origin
+    looking down +z, fx = fy = 30, principal point (20, 12), so that u = 20 + 30 x / z and v = 12 + 30 y / z; the
+    clamp bounds are x in [-6, 44.85], y in [-3.6, 26.45].  Rows: 0, 4, 5 ordinary; 1 a large splat with u = -10 (left
+    of the bound by 4 px, still reaching the image); 3 a large splat with v = 35 (below the lower bound by 8.55 px);
+    2 a small splat at u = 140, culled.  Returns (the six projection inputs in float64, image size, depth range)."""
+    position = torch.tensor([[0.0, 0.0, 3.0], [-3.0, 0.2, 3.0], [8.0, 0.3, 2.0], [0.5, 2.3, 3.0], [0.4, -0.3, 2.5],
+                             [-0.6, 0.5, 4.0]], dtype=F64)
+    log_scaling = torch.tensor([[-1.6, -1.2, -2.0], [0.5, 0.2, 0.35], [-3.0, -3.2, -2.8], [0.1, 0.3, -0.2],
+                                [-1.0, -2.0, -1.5], [-0.7, -1.4, -1.1]], dtype=F64)
+    rotation = torch.tensor([[0.1, 0.2, 0.3, 0.9], [0.5, -0.3, 0.2, 0.7], [0.0, 0.0, 0.0, 1.0], [-0.4, 0.1, 0.6, 0.5],
+                             [0.3, 0.3, -0.2, 1.1], [-0.2, 0.7, 0.1, 0.6]], dtype=F64)
+    alpha_logit = torch.tensor([[0.5], [1.0], [0.0], [0.8], [-0.5], [1.5]], dtype=F64)
+    T_camera_world = torch.eye(4, dtype=F64)
+    projection = torch.tensor([30.0, 30.0, 20.0, 12.0], dtype=F64)
+    return (position, log_scaling, rotation, alpha_logit, T_camera_world, projection), (40, 24), (0.1, 100.0)
+
+
+def test_projection_gradcheck_clamp_and_cull():
+    """gradcheck through the clamp's zero-gradient branch and past a culled row"""
+    inputs, size, depth_range = clamp_and_cull_scene()
+    margin = 0.15  # the default clamp_margin of apply()
+    ref_points, _, ref_idx = orc.project(*(t.numpy() for t in inputs), size, depth_range)
+    u, v = ref_points[:, 0], ref_points[:, 1]
+    lo_x, hi_x, lo_y, hi_y = -size[0] * margin, (size[0] - 1) * (1 + margin), -size[1] * margin, \
+        (size[1] - 1) * (1 + margin)
+    assert (u < lo_x).any(), "scene must hold a visible Gaussian left of the clamp margin"
+    culled = np.setdiff1d(np.arange(6), ref_idx)
+    assert culled.size >= 1, "scene must hold a culled Gaussian"
+    away = 1e-3 * size[0]  # the clamp is not differentiable at its bounds
+    assert min(np.abs(u - lo_x).min(), np.abs(u - hi_x).min(), np.abs(v - lo_y).min(), np.abs(v - hi_y).min()) >= away
+    leaves = [t.to(DEV).requires_grad_(True) for t in inputs]
+    points, depth, idx = hip_proj.apply(*leaves, size, depth_range)
+    assert (pu.to_np(idx) == ref_idx).all()
+    (points.sum() + depth.sum()).backward()
+    for t in leaves[:4]:
+        assert float(t.grad[culled].abs().sum()) == 0.0 and float(t.grad.abs().sum()) > 0.0
+
+    def fn(*t):
+        points, depth, _ = hip_proj.apply(*t, size, depth_range)
+        return points, depth
+    assert gradcheck(fn, [t.detach().requires_grad_(True) for t in leaves], **GRADCHECK)
+
+
 @pytest.mark.parametrize("degree", [0, 1, 2, 3])
 def test_sh_gradcheck_repeated_indexes(degree):
     torch.manual_seed(degree)
