@@ -49,6 +49,26 @@ static inline int gs_check_background(const char* what, int blend, bool has_back
   return GS_OK;
 }
 
+// what every f32 rasterizer entry point refuses alike: an empty image, a feature width outside [1, max_features]
+static inline int gs_check_raster_call(const char* what, int width, int height, int num_features, int max_features) {
+  GS_REQUIRE(width > 0 && height > 0, GS_ERR_INVALID_ARGUMENT, "%s: image size %dx%d", what, width, height);
+  GS_REQUIRE(num_features >= 1 && num_features <= max_features, GS_ERR_UNSUPPORTED,
+             "%s: feature width %d not in [1,%d]", what, num_features, max_features);
+  return GS_OK;
+}
+
+// ... and the two forwards (the visibility buffer: where the configuration asks for it, `vis`, and v > 0)
+static inline int gs_check_raster_fwd_buffers(const char* what, const void* image, const void* alpha,
+                                              const void* tile_ranges, int64_t k, const void* points,
+                                              const void* features, const void* overlap_to_point, bool vis,
+                                              const void* visibility, int64_t v) {
+  GS_REQUIRE(image && alpha && tile_ranges, GS_ERR_INVALID_ARGUMENT, "%s: NULL output or ranges", what);
+  GS_REQUIRE(k == 0 || (points && features && overlap_to_point), GS_ERR_INVALID_ARGUMENT,
+             "%s: NULL input with %lld overlaps", what, (long long)k);
+  GS_REQUIRE(!vis || visibility || v == 0, GS_ERR_INVALID_ARGUMENT, "%s: visibility buffer is NULL", what);
+  return GS_OK;
+}
+
 // ---- screen-tile sharding (GsRowShard, include/gsplat_hip.h): owned tile rows <-> local rows.  Plain struct
 // arithmetic, usable on host and device.  `rows` = tile rows of the full image.
 struct GsShard {

@@ -1,7 +1,8 @@
 // raster_bwd.hip -- gradient backward of the alpha-blend (reference rasterizer/backward.py:53-228,
 // pdf gradients taichi_lib/generic.py:321-336 / :371-404).
 //
-// Same wave-per-16x16-region layout, LDS staging and scalar sub-block masks as raster_fwd.hip.
+// Same wave-per-16x16-region layout, LDS staging and scalar sub-block masks as raster_fwd.hip, from the same code
+// (raster_walk.h); MODE 2's plain pdf, pdf gradients and per-pixel sums are raster_pdf.h, shared with raster_wide.hip.
 // What is specific to the backward:
 //   * Front-to-back re-traversal with the FINAL image as the "remaining colour"
 //     (backward.py:110,177-180).  The remaining colour only ever appears dotted with the pixel's
@@ -24,6 +25,7 @@
 
 #include "gs_common.h"
 #include "raster_pdf.h"
+#include "raster_walk.h"
 
 namespace {
 
@@ -54,14 +56,6 @@ struct BwdArgs {
   const float* alpha;
   const float* grad_weight;
 };
-
-// pixel origin of a (local) tile in the full image, and the row of the image buffers it starts at
-__device__ __forceinline__ void tile_origin(const BwdArgs& a, int tile, int& x0, int& y0, int& yout0) {
-  const int lty = tile / a.tiles_wide;
-  x0 = (tile - lty * a.tiles_wide) * a.tile_size;
-  y0 = gs_shard_global_row(a.sh, lty) * a.tile_size;
-  yout0 = lty * a.tile_size;
-}
 
 // LDS arena of one wave: sized by the 64-splat staging group, not by the wave's pixel region
 // MODE 0: lean (6 ellipse-frame moments); 1: lean + the two densification heuristics (training with statistics);
@@ -166,8 +160,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
   const int range_x = __builtin_amdgcn_readfirstlane(range_v.x), range_y = __builtin_amdgcn_readfirstlane(range_v.y);
   // lean kernels stage the ellipse frame scaled by K_EXP so that the pdf is exp2(-(tx^2 + ty^2)) with no further
   // multiply; the moments are accumulated in those coordinates and unscaled once per splat in the epilogue
-  constexpr float K_EXP = 0.84932180028801904f;  // sqrt(0.5 * log2(e))
-  constexpr float IK = 1.0f / K_EXP, IK2 = IK * IK;
+  constexpr float IK = 1.0f / GS_K_EXP, IK2 = IK * IK;
 
   int zero_off = 0;  // byte offset of the zeros read at the head of every splat (see above)
   for (int g0 = range_x; g0 < range_y; g0 += 64) {
@@ -186,49 +179,13 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
     int staged_mask = 0;
     if (lane < cnt) {
       idx = a.o2p[g0 + lane];
-      const float* p = a.points + int64_t(idx) * 7;
-      const float mx = p[0], my = p[1];
-      ax = p[2]; ay = p[3];
-      isx = gs_rcp_fast(p[4]); isy = gs_rcp_fast(p[5]);  // v_rcp_f32: 1 ulp, far inside the parity tolerance
-      al = p[6];
-      const float ks = FULL ? 1.0f : K_EXP;
-      const float Ax = ax * isx * ks, Ay = ay * isx * ks, Bx = -ay * isy * ks, By = ax * isy * ks;
-      int mask = 0;
-      if (FULL && a.aa) {
-        float s1, s2, u0, u1;
-        s_sig_grad(0.5f, isx, s1, u0, u1);
-        s_sig_grad(0.5f, isy, s2, u0, u1);
-        // D(0; s) = S(0.5 / s) - S(-0.5 / s) = 2 S(0.5 / s) - 1
-        mask = gs_sub_block_mask_antialias<NB>(ax, ay, p[4], p[5], al, a.inv_thr, 2.0f * s1 - 1.0f, 2.0f * s2 - 1.0f,
-                                               float(x0) + 0.5f - mx, float(y0) + 0.5f - my);
-      } else if (al > a.thr) {
-        // alpha * pdf > thr  needs  tx^2 + ty^2 < log2(alpha / thr)  (scaled frame; 2 ln(alpha / thr) unscaled)
-        const float r2 = __log2f(al * a.inv_thr) * (FULL ? 1.38629436111989f : 1.0f);
-        mask = gs_sub_block_mask<NB>(Ax, Ay, Bx, By, r2, float(x0) + 0.5f - mx, float(y0) + 0.5f - my);
-      }
-      staged_mask = mask;
-      if (FULL && a.aa) {
-        // antialiased pdf: the per-pixel code works in the splat's frame (ux, uy) and needs the sigmas and the half
-        // pixel in sigma units, not the scaled ellipse frame
-        s_geo[lane][0] = make_float4(mx, my, p[4], p[5]);
-        s_geo[lane][1] = make_float4(0.5f * isx, 0.5f * isy, al, __int_as_float(mask));
-      } else {
-        // lean: tx = A . (X - origin) + A . (origin - m), the second term formed here (the forward's expression)
-        const float ox = float(x0) - mx, oy = float(y0) - my;
-        if (FULL) s_geo[lane][0] = make_float4(mx, my, Ax, Ay);
-        else s_geo[lane][0] = make_float4(__builtin_fmaf(Ax, ox, Ay * oy), __builtin_fmaf(Bx, ox, By * oy), Ax, Ay);
-        // lean modes carry -log2(opacity): it starts the exponent's fma chain, so v_exp_f32 returns alpha itself
-        s_geo[lane][1] = make_float4(Bx, By, FULL ? al : -__log2f(al), __int_as_float(mask));
-      }
-      if (FULL) s_geo[lane][2] = make_float4(ax, ay, isx, isy);
-      const float* f = a.features + int64_t(idx) * a.F;
-#pragma unroll
-      for (int q = 0; q < REC_V4 - GEO_V4; ++q) {
-        float fv[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) fv[k] = (4 * q + k < FP && 4 * q + k < a.F) ? f[4 * q + k] : 0.0f;
-        s_geo[lane][GEO_V4 + q] = make_float4(fv[0], fv[1], fv[2], fv[3]);
-      }
+      const GsSplat sp = gs_load_splat(a.points + int64_t(idx) * 7);
+      ax = sp.ax; ay = sp.ay; isx = sp.isx; isy = sp.isy; al = sp.al;
+      // the record's geometry and the conservative sub-block mask: the forward's own expressions (raster_walk.h), so a
+      // pixel is hit here exactly when it was there
+      staged_mask = FULL ? gs_stage_general<NB, true>(s_geo[lane], sp, x0, y0, a.thr, a.inv_thr, a.aa, true)
+                         : gs_stage_lean<NB>(s_geo[lane], sp, x0, y0, a.thr, a.inv_thr);
+      gs_stage_features<FP, GEO_V4>(s_geo[lane], a.features + int64_t(idx) * a.F, a.F);
     }
 #pragma unroll
     for (int c = 0; c < NACC; ++c) s_acc[lane][c] = 0.0f;
@@ -240,14 +197,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
       g0v = s_geo[j][0];
       g1v = s_geo[j][1];
       if (FULL) g2v = s_geo[j][2];
-#pragma unroll
-      for (int q = 0; q < REC_V4 - GEO_V4; ++q) {
-        const float4 fq = s_geo[j][GEO_V4 + q];
-        const float fv[4] = {fq.x, fq.y, fq.z, fq.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (4 * q + k < FP) feat[4 * q + k] = fv[k];
-      }
+      gs_fetch_features<FP, GEO_V4>(s_geo[j], feat);
     };
     fetch_record(0);
     uint64_t reach[NB];
@@ -291,38 +241,22 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
         float dmx = 0, dmy = 0, dax = 0, day = 0, dsx = 0, dsy = 0;
         float Px = 0, Py = 0;  // antialias: d pdf / d (ux, uy), the splat-frame gradient the mean and axis terms share
         float aa_z[4] = {0, 0, 0, 0}, aa_a[4] = {0, 0, 0, 0};  // antialias: sigmoid arguments and values
+        // (the antialiased pdf's value half stays written out, here and in raster_wide.hip: as a call these kernels take
+        // more registers; the rest of the general mode is raster_pdf.h, where the formulas and the record's layout are)
         if (FULL && a.aa) {
-          // taichi_lib/generic.py:341-404 in the splat's frame: u = R(axis) d, pdf = tau fx(ux) fy(uy) with
-          // f(u; s) = s (S((u + .5) / s) - S((u - .5) / s)).  With a_k = S(z_k), d_k = S'(z_k), z_1,2 = (u +- .5) / s:
-          //   df/du = d_1 - d_2,   df/ds = (a_1 - a_2) - (z_1 d_1 - z_2 d_2)
-          // record: g0 = (mean, sx, sy), g1 = (.5 / sx, .5 / sy, alpha, mask), g2 = (axis, 1 / sx, 1 / sy)
-          const float axv = g2v.x, ayv = g2v.y;
-          const float ux = dx * axv + dy * ayv, uy = dy * axv - dx * ayv;
-          const float zx1 = __builtin_fmaf(ux, g2v.z, g1v.x), zx2 = __builtin_fmaf(ux, g2v.z, -g1v.x);
-          const float zy1 = __builtin_fmaf(uy, g2v.w, g1v.y), zy2 = __builtin_fmaf(uy, g2v.w, -g1v.y);
-          aa_z[0] = zx1; aa_z[1] = zx2; aa_z[2] = zy1; aa_z[3] = zy2;
+          const float ux = dx * g2v.x + dy * g2v.y, uy = dy * g2v.x - dx * g2v.y;
+          aa_z[0] = __builtin_fmaf(ux, g2v.z, g1v.x); aa_z[1] = __builtin_fmaf(ux, g2v.z, -g1v.x);
+          aa_z[2] = __builtin_fmaf(uy, g2v.w, g1v.y); aa_z[3] = __builtin_fmaf(uy, g2v.w, -g1v.y);
 #pragma unroll
           for (int k = 0; k < 4; ++k) aa_a[k] = s_sig_value(aa_z[k]);
-          const float Dx = aa_a[0] - aa_a[1], Dy = aa_a[2] - aa_a[3];
-          const float fx = g0v.z * Dx, fy = g0v.w * Dy;
-          p = 6.28318530717958648f * fx * fy;
-          // the derivatives follow behind the hit test (aa_gradients below)
+          p = 6.28318530717958648f * (g0v.z * (aa_a[0] - aa_a[1])) * (g0v.w * (aa_a[2] - aa_a[3]));
+        } else if (FULL) {
+          p = gs_general_pdf_plain(dx, dy, g0v, g1v, g2v, tx, ty, dmx, dmy, dax, day, dsx, dsy);
         } else {
-          tx = FULL ? dx * g0v.z + dy * g0v.w : __builtin_fmaf(g0v.z, Xf[b], __builtin_fmaf(g0v.w, Yf[b], g0v.x));
-          ty = FULL ? dx * g1v.x + dy * g1v.y : __builtin_fmaf(g1v.x, Xf[b], __builtin_fmaf(g1v.y, Yf[b], g0v.y));
-          // lean: the record carries -log2(opacity), p is alpha itself (same expression as the forward: same bits)
-          p = FULL ? gs_exp2_fast(-0.72134752044448170f * (tx * tx + ty * ty))
-                   : gs_exp2_fast(-__builtin_fmaf(ty, ty, __builtin_fmaf(tx, tx, g1v.z)));
-          if (FULL) {
-            // taichi_lib/generic.py:321-336
-            const float txs = tx * g2v.z, tys = ty * g2v.w;
-            dsx = tx * tx * p * g2v.z;
-            dsy = ty * ty * p * g2v.w;
-            dax = p * (txs * -dx + tys * -dy);
-            day = p * (txs * -dy + tys * dx);
-            dmx = p * (txs * g2v.x - tys * g2v.y);
-            dmy = p * (txs * g2v.y + tys * g2v.x);
-          }
+          tx = __builtin_fmaf(g0v.z, Xf[b], __builtin_fmaf(g0v.w, Yf[b], g0v.x));
+          ty = __builtin_fmaf(g1v.x, Xf[b], __builtin_fmaf(g1v.y, Yf[b], g0v.y));
+          // the record carries -log2(opacity), p is alpha itself (same expression as the forward: same bits)
+          p = gs_exp2_fast(-__builtin_fmaf(ty, ty, __builtin_fmaf(tx, tx, g1v.z)));
         }
         const float alpha_raw = FULL ? g1v.z * p : p;
         const bool over = alpha_raw > a.thr, open = Tr[b] > tsat;
@@ -333,20 +267,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
         // under EXEC = the pixels that take something from this splat (a partly empty EXEC costs a wave64 instruction
         // nothing extra), so nobody has to zero alpha for the others.
         if (!hit) continue;
-        if (FULL && a.aa) {  // aa_gradients: see the value half above
-          const float d0 = s_sig_slope(aa_z[0], aa_a[0]), d1 = s_sig_slope(aa_z[1], aa_a[1]);
-          const float d2 = s_sig_slope(aa_z[2], aa_a[2]), d3 = s_sig_slope(aa_z[3], aa_a[3]);
-          const float Dx = aa_a[0] - aa_a[1], Dy = aa_a[2] - aa_a[3];
-          const float tau = 6.28318530717958648f;
-          const float fxt = tau * (g0v.z * Dx), fyt = tau * (g0v.w * Dy);
-          Px = (d0 - d1) * fyt;
-          Py = fxt * (d2 - d3);
-          dsx = (Dx - __builtin_fmaf(aa_z[0], d0, -(aa_z[1] * d1))) * fyt;
-          dsy = fxt * (Dy - __builtin_fmaf(aa_z[2], d2, -(aa_z[3] * d3)));
-          dax = __builtin_fmaf(Px, dx, Py * dy);
-          day = __builtin_fmaf(Px, dy, -(Py * dx));
-          // dmx, dmy: the wave totals of aag Px, aag Py are rotated out of the frame once per splat (epilogue)
-        }
+        if (FULL && a.aa) gs_general_pdf_gradient(dx, dy, g0v, aa_z, aa_a, Px, Py, dax, day, dsx, dsy);
         const float alc = __builtin_amdgcn_fmed3f(alpha_raw, a.cmax, -1.0f);  // min(alpha, cmax), one v_med3_f32 (:169)
         float dot = 0.0f;
 #pragma unroll
@@ -360,23 +281,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
 #pragma unroll
         for (int c = 0; c < FP; ++c) gf[c] += w * gpix[b][c];  // :201
         if (FULL) {
-          const float aag = g1v.z * alpha_grad;  // :184
-          if (a.aa) {
-            S[0] += aag * Px; S[1] += aag * Py;  // splat frame; see the epilogue
-            if (a.heur) {
-              dmx = -Px * g2v.x + Py * g2v.y;
-              dmy = -Px * g2v.y - Py * g2v.x;
-            }
-          } else {
-            S[0] += aag * dmx; S[1] += aag * dmy;
-          }
-          S[2] += aag * dax; S[3] += aag * day;
-          S[4] += aag * dsx; S[5] += aag * dsy;
-          S[6] += p * alpha_grad;
-          if (a.heur) {
-            S[7] += aag * aag;                                  // :194-198
-            S[8] += fabsf(aag * dmx) + fabsf(aag * dmy);
-          }
+          gs_general_sums<true>(a.aa, a.heur, g1v, g2v, p, dmx, dmy, dax, day, dsx, dsy, Px, Py, alpha_grad, S);
         } else {
           // moments in the (scaled) ellipse frame (tx, ty are O(1): no cancellation for elongated splats), carrying
           // the splat's opacity: G = alpha_p * pdf * dL/dalpha
@@ -457,10 +362,7 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
         if (FULL) {
 #pragma unroll
           for (int c = 0; c < 7; ++c) row[c] = t[c];
-          if (a.aa) {  // the mean's gradient out of the splat frame: d ux / d mean = -axis, d uy / d mean = -perp(axis)
-            row[0] = -t[0] * ax + t[1] * ay;
-            row[1] = -t[0] * ay - t[1] * ax;
-          }
+          if (a.aa) gs_mean_grad_from_splat_frame(row[0], row[1], ax, ay);
           if (a.heur) { row[7 + FP] = t[7]; row[8 + FP] = t[8]; }
         } else {
           // t = wave totals of (G, G tx, G ty, G tx^2, G tx ty, G ty^2), tx = d.axis/sx, ty = d.perp(axis)/sy.
@@ -513,47 +415,21 @@ __device__ __forceinline__ void raster_bwd_body(const BwdArgs& a, int tile, int 
   }
 }
 
-// Block -> work: see raster_fwd_kernel (the mapper's fullest tiles get one workgroup per 8x8 quadrant).
+// Block -> work: gs_raster_region (raster_walk.h; the mapper's fullest tiles get one workgroup per 8x8 quadrant).
 template <int NB, int FP, int MODE>
 __global__ __launch_bounds__(64) void raster_bwd_kernel(const BwdArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[BwdShape<FP, MODE>::ARENA_F];
   // the 64-byte block of zeros that every splat's sums start from (raster_bwd_body)
   __shared__ __attribute__((aligned(16))) float s_zeros[16];
   if (threadIdx.x < 16) s_zeros[threadIdx.x] = 0.0f;  // read after the first staging barrier
-  const int per_tile = a.sub_x * a.sub_y;
-  constexpr int RW = NB == 1 ? 8 : 16, RH = NB == 4 ? 16 : 8;  // the wave's pixel region: NB 8x8 sub-blocks
-  int tile, quad;
-  if (a.tile_order) {
-    const int b = blockIdx.x;
-    const int heavy = (NB > 1 && a.heavy) ? min(*a.heavy, a.heavy_cap) : 0;
-    if (NB > 1 && b < 4 * heavy) {
-      tile = a.tile_order[b >> 2];
-      int x0, y0, yout0;
-      tile_origin(a, tile, x0, y0, yout0);
-      x0 += (b & 1) * 8; y0 += ((b >> 1) & 1) * 8; yout0 += ((b >> 1) & 1) * 8;
-      if (x0 < a.W && y0 < a.H) raster_bwd_body<1, FP, MODE>(a, tile, x0, y0, yout0, smem, s_zeros);
-      return;
-    }
-    const int c = b - 4 * heavy, rank = heavy + c / per_tile;
-    if (rank >= a.num_tiles) return;
-    tile = a.tile_order[rank];
-    quad = c % per_tile;
-  } else {
-    const int item = gs_xcd_remap(blockIdx.x, a.num_items);
-    if (item < 0) return;
-    tile = item / per_tile;
-    quad = item - tile * per_tile;
-  }
-  int x0, y0, yout0;
-  tile_origin(a, tile, x0, y0, yout0);
-  x0 += (quad % a.sub_x) * RW; y0 += (quad / a.sub_x) * RH; yout0 += (quad / a.sub_x) * RH;
-  if (x0 >= a.W || y0 >= a.H) return;
-  raster_bwd_body<NB, FP, MODE>(a, tile, x0, y0, yout0, smem, s_zeros);
+  gs_raster_region<NB>(a, [&](auto nb, int tile, int x0, int y0, int yout0) {
+    raster_bwd_body<decltype(nb)::value, FP, MODE>(a, tile, x0, y0, yout0, smem, s_zeros);
+  });
 }
 
 template <int NB, int MODE>
 int launch_fp(const BwdArgs& a, hipStream_t s) {
-  const int grid = 8 * int(gs_div_up(a.num_items + (a.heavy ? 4 * a.heavy_cap : 0), 8));
+  const int grid = gs_raster_grid(a);
   if (a.F <= 3) hipLaunchKernelGGL((raster_bwd_kernel<NB, 3, MODE>), dim3(grid), dim3(64), 0, s, a);
   else if (a.F <= 5) hipLaunchKernelGGL((raster_bwd_kernel<NB, 5, MODE>), dim3(grid), dim3(64), 0, s, a);
   else if (a.F <= 8) hipLaunchKernelGGL((raster_bwd_kernel<NB, 8, MODE>), dim3(grid), dim3(64), 0, s, a);
@@ -587,35 +463,21 @@ extern "C" int gs_raster_bwd(int64_t v, int32_t num_features, const float* point
   if (int rc = gs_check_cfg(cfg)) return rc;
   GS_REQUIRE(!grad_weight || alpha, GS_ERR_INVALID_ARGUMENT,
              "gs_raster_bwd: grad_weight without the forward's alpha image");
-  GS_REQUIRE(width > 0 && height > 0, GS_ERR_INVALID_ARGUMENT, "gs_raster_bwd: image size %dx%d", width, height);
-  GS_REQUIRE(num_features >= 1 && num_features <= GS_MAX_FEATURES, GS_ERR_UNSUPPORTED,
-             "gs_raster_bwd: feature width %d not in [1,%d]", num_features, GS_MAX_FEATURES);
+  if (int rc = gs_check_raster_call("gs_raster_bwd", width, height, num_features, GS_MAX_FEATURES)) return rc;
   GS_REQUIRE(image && grad_image && tile_ranges, GS_ERR_INVALID_ARGUMENT, "gs_raster_bwd: NULL image or ranges");
   GS_REQUIRE(cfg->use_alpha_blending, GS_ERR_UNSUPPORTED,
              "gs_raster_bwd: no gradient is defined without alpha blending (reference tests/test_rasterizer.py:92-101)");
   if (k == 0 || v == 0) return GS_OK;
   GS_REQUIRE(points && features && overlap_to_point && grad_rows, GS_ERR_INVALID_ARGUMENT,
              "gs_raster_bwd: NULL input");
-  const int ts = cfg->tile_size;
   BwdArgs a;
   a.points = points; a.features = features; a.ranges = reinterpret_cast<const int2*>(tile_ranges);
   a.o2p = overlap_to_point; a.image = image; a.grad_image = grad_image; a.grad_rows = grad_rows;
   a.W = width; a.H = height; a.F = num_features;
   a.row_floats = gs_grad_row_floats(num_features);
-  a.tiles_wide = int(gs_div_up(width, ts));
-  a.tile_size = ts;
-  if (int rc = gs_make_shard(shard, int(gs_div_up(height, ts)), &a.sh)) return rc;
-  const int num_tiles = a.tiles_wide * a.sh.local_rows;
-  if (num_tiles == 0) return GS_OK;
-  const int nb = gs_raster_sub_blocks(cfg, num_tiles, 1);
-  a.sub_x = ts / (nb == 1 ? 8 : 16);
-  a.sub_y = ts / (nb == 4 ? 16 : 8);
-  a.num_items = num_tiles * a.sub_x * a.sub_y;
-  a.tile_order = tile_order;
-  a.num_tiles = num_tiles;
-  a.heavy = (tile_order && ts == 16 && nb > 1) ? heavy_tiles : nullptr;
-  a.heavy_cap = num_tiles / 4;
-  if (cfg->tune_no_heavy_split) a.heavy = nullptr;
+  int nb = 0;
+  if (int rc = gs_raster_geometry(a, cfg, width, height, tile_order, heavy_tiles, shard, 1, nb)) return rc;
+  if (a.num_tiles == 0) return GS_OK;
   a.cmax = cfg->clamp_max_alpha; a.thr = cfg->alpha_threshold; a.sat = cfg->saturate_threshold;
   a.inv_thr = 1.0f / cfg->alpha_threshold;
   a.aa = cfg->antialias; a.heur = cfg->compute_point_heuristic;

@@ -18,12 +18,15 @@
 //     to evaluating every pixel: a skipped pixel would have failed `alpha > alpha_threshold`.
 //   * Launch: grid = regions, XCD-aware remap so that neighbouring tiles (which gather the same
 //     splat rows) share an L2.
+// Block -> region, the launch geometry and the geometry words of a splat's record are raster_walk.h, shared with
+// raster_bwd.hip and raster_wide.hip; MODE 2's per-pixel alpha is raster_pdf.h.  The lean modes' arithmetic is here.
 //
 // Roofline: algorithmic HBM bytes K*(4 + 28 + 4F) + 16T + 4P(F+1); the kernel is
 // VALU-bound (about 20 VALU + 1 v_exp_f32 per evaluated pixel-splat pair).
 
 #include "gs_common.h"
 #include "raster_pdf.h"
+#include "raster_walk.h"
 
 namespace {
 
@@ -54,14 +57,6 @@ struct FwdArgs {
   int bg_off;
 };
 
-// pixel origin of a (local) tile in the full image, and the row of the output buffer it starts at
-__device__ __forceinline__ void tile_origin(const FwdArgs& a, int tile, int& x0, int& y0, int& yout0) {
-  const int lty = tile / a.tiles_wide;
-  x0 = (tile - lty * a.tiles_wide) * a.tile_size;
-  y0 = gs_shard_global_row(a.sh, lty) * a.tile_size;
-  yout0 = lty * a.tile_size;
-}
-
 // NB: 8x8 sub-blocks per wave (1, 2 or 4; gs_raster_sub_blocks picks it from the grid size).  FP: padded feature width.
 // MODE 3: lean quantile pass (no blending, no antialias, no statistics: the median-depth pass of renderer.py:203-208);
 // MODE 0: blend only (lean); 1: blend + per-splat visibility (training with pruning statistics);
@@ -74,7 +69,7 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
                                                 float4 (*s_geo)[(MODE == 2 ? 3 : 2) + (FP + 3) / 4], float* s_vis,
                                                 int* s_idx) {
   // staged record of a splat: GEO_V4 float4s of geometry, then its feature row (one LDS address, b128 reads)
-  constexpr int GEO_V4 = MODE == 2 ? 3 : 2, FEAT_V4 = (FP + 3) / 4;
+  constexpr int GEO_V4 = MODE == 2 ? 3 : 2;
   constexpr bool FULL = MODE == 2, VIS = MODE == 1 || MODE == 2, QUANT = MODE == 3;
   const bool blend = QUANT ? false : (FULL ? a.blend != 0 : true);
   const int lane = threadIdx.x;
@@ -99,7 +94,6 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
   int2 range;  // wave-uniform: loop bounds in scalar registers
   range.x = __builtin_amdgcn_readfirstlane(range_v.x);
   range.y = __builtin_amdgcn_readfirstlane(range_v.y);
-  const float k_exp = 0.84932180028801904f;  // sqrt(0.5 * log2(e)): exp(-0.5 t^2) = exp2(-(k t)^2)
 
   for (int g0 = range.x; g0 < range.y; g0 += 64) {
     // The reference's forward never stops (forward.py:84-128).  Once every pixel of the region has less than
@@ -125,39 +119,19 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
     // ---- stage up to 64 splats: lane j <- splat g0 + j
     if (lane < cnt) {
       const int idx = a.o2p[g0 + lane];
-      const float* p = a.points + int64_t(idx) * 7;
-      const float mx = p[0], my = p[1], ax = p[2], ay = p[3], sx = p[4], sy = p[5], al = p[6];
-      const float isx = gs_rcp_fast(sx), isy = gs_rcp_fast(sy);  // v_rcp_f32: 1 ulp
-      const float Ax = ax * isx * k_exp, Ay = ay * isx * k_exp;
-      const float Bx = -ay * isy * k_exp, By = ax * isy * k_exp;
-      // conservative sub-block mask: alpha*exp2(-(tx^2+ty^2)) > thr needs tx^2+ty^2 < log2(alpha/thr)
-      int mask = 0;
-      if (FULL && a.aa) {
-        mask = gs_sub_block_mask_antialias<NB>(ax, ay, sx, sy, al, a.inv_thr, s_sig(0.5f, isx) - s_sig(-0.5f, isx),
-                                               s_sig(0.5f, isy) - s_sig(-0.5f, isy), float(x0) + 0.5f - mx,
-                                               float(y0) + 0.5f - my);
-      } else if (al > a.thr) {
-        mask = gs_sub_block_mask<NB>(Ax, Ay, Bx, By, __log2f(al * a.inv_thr), float(x0) + 0.5f - mx,
-                                     float(y0) + 0.5f - my);
-      }
-      staged_mask = mask;
-      // Lean modes: the ellipse-frame coordinates of a pixel are tx = A . (X - m) = A . (X - origin) + A . (origin - m):
-      // the second term is formed once per (region, splat) here, and a pixel's tx is two fma on its origin-relative
-      // centre (|X - origin| < 16: no cancellation beyond what X - m has) instead of two subtractions, a multiply and
-      // an fma.  The backward uses the same expression: same bits, same hit / miss per pixel.
-      const float ox = float(x0) - mx, oy = float(y0) - my;
-      if (FULL) s_geo[lane][0] = make_float4(mx, my, Ax, Ay);
-      else s_geo[lane][0] = make_float4(__builtin_fmaf(Ax, ox, Ay * oy), __builtin_fmaf(Bx, ox, By * oy), Ax, Ay);
-      // lean modes carry -log2(opacity): it starts the exponent's fma chain, so v_exp_f32 returns alpha itself
-      s_geo[lane][1] = make_float4(Bx, By, FULL ? al : -__log2f(al), __int_as_float(mask));
-      if (FULL) s_geo[lane][2] = make_float4(ax, ay, isx, isy);
+      const GsSplat sp = gs_load_splat(a.points + int64_t(idx) * 7);
+      // the record's geometry and the conservative sub-block mask (raster_walk.h; the backward stages the same words)
+      staged_mask = FULL ? gs_stage_general<NB, false>(s_geo[lane], sp, x0, y0, a.thr, a.inv_thr, a.aa, true)
+                         : gs_stage_lean<NB>(s_geo[lane], sp, x0, y0, a.thr, a.inv_thr);
       if (VIS) {
         s_vis[lane] = 0.0f;
         s_idx[lane] = idx;
       }
+      // the feature row -> the record's float4 words.  Written out: as a call of the backward's gs_stage_features it
+      // splits two s_waitcnt inside raster_fwd_kernel<4, 8, 3>'s blend loop (profiles/raster_walk/isa_identity.txt)
       const float* f = a.features + int64_t(idx) * a.F;
 #pragma unroll
-      for (int q = 0; q < FEAT_V4; ++q) {
+      for (int q = 0; q < (FP + 3) / 4; ++q) {
         float fv[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) fv[k] = (4 * q + k < FP && 4 * q + k < a.F) ? f[4 * q + k] : 0.0f;
@@ -179,14 +153,7 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
       r.g0 = s_geo[jj][0];
       r.g1 = s_geo[jj][1];
       if (FULL) r.g2 = s_geo[jj][2];
-#pragma unroll
-      for (int q = 0; q < FEAT_V4; ++q) {
-        const float4 fq = s_geo[jj][GEO_V4 + q];
-        const float fv[4] = {fq.x, fq.y, fq.z, fq.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (4 * q + k < FP) r.f[4 * q + k] = fv[k];
-      }
+      gs_fetch_features<FP, GEO_V4>(s_geo[jj], r.f);
     };
     // the staged splats' sub-block masks as four scalar ballots (see raster_bwd.hip)
     uint64_t reach[NB];
@@ -207,27 +174,13 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         if (!(mask & (1 << b))) continue;  // scalar branch
-        const float dx = FULL ? Xf[b] - g0v.x : 0.0f, dy = FULL ? Yf[b] - g0v.y : 0.0f;
-        float p, alpha;
-        if (FULL && a.aa) {
-          // taichi_lib/generic.py:347-357
-          const float tx = dx * g2v.x + dy * g2v.y, ty = dy * g2v.x - dx * g2v.y;
-          float nx, dx_, ny, dy_;
-          aa_axis(tx, g2v.z, nx, dx_);
-          aa_axis(ty, g2v.w, ny, dy_);
-          // tau sx sy D(tx) D(ty); sx sy = 1 / (isx isy) goes into the same reciprocal
-          p = 6.28318530717958648f * nx * ny * gs_rcp_fast(dx_ * dy_ * g2v.z * g2v.w);
-          alpha = g1v.z * p;
+        float alpha;
+        if (FULL) {
+          alpha = gs_general_alpha(a.aa, Xf[b] - g0v.x, Yf[b] - g0v.y, g0v, g1v, g2v);
         } else {
-          const float tx = FULL ? dx * g0v.z + dy * g0v.w
-                                : __builtin_fmaf(g0v.z, Xf[b], __builtin_fmaf(g0v.w, Yf[b], g0v.x));
-          const float ty = FULL ? dx * g1v.x + dy * g1v.y
-                                : __builtin_fmaf(g1v.x, Xf[b], __builtin_fmaf(g1v.y, Yf[b], g0v.y));
-          if (FULL) {
-            alpha = g1v.z * gs_exp2_fast(-(tx * tx + ty * ty));
-          } else {
-            alpha = gs_exp2_fast(-__builtin_fmaf(ty, ty, __builtin_fmaf(tx, tx, g1v.z)));  // opacity * pdf
-          }
+          const float tx = __builtin_fmaf(g0v.z, Xf[b], __builtin_fmaf(g0v.w, Yf[b], g0v.x));
+          const float ty = __builtin_fmaf(g1v.x, Xf[b], __builtin_fmaf(g1v.y, Yf[b], g0v.y));
+          alpha = gs_exp2_fast(-__builtin_fmaf(ty, ty, __builtin_fmaf(tx, tx, g1v.z)));  // opacity * pdf
         }
         const float al = __builtin_amdgcn_fmed3f(alpha, a.cmax, -1.0f);  // min(alpha, cmax) (forward.py:98-99)
         bool hit = al > a.thr;
@@ -287,49 +240,20 @@ __device__ __forceinline__ void raster_fwd_body(const FwdArgs& a, int tile, int 
   }
 }
 
-// Block -> work.  With a launch order from the mapper: its first `*heavy` tiles (the fullest ones; tile_size 16
-// only) are rasterized by FOUR workgroups each, one per 8x8 quadrant, the others by workgroups of the grid's
-// own wave region -- a launch cannot end before its fullest tile has been walked by one wave, which is what
-// bounds small grids (strips of a sharded frame, training-size images).  Without an order: XCD-contiguous bands.
+// Block -> work: gs_raster_region (raster_walk.h; the mapper's fullest tiles get one workgroup per 8x8 quadrant).
 template <int NB, int FP, int MODE>
 __global__ __launch_bounds__(64) void raster_fwd_kernel(const FwdArgs a) {
   __shared__ float4 s_geo[64][(MODE == 2 ? 3 : 2) + (FP + 3) / 4];
   __shared__ float s_vis[(MODE == 1 || MODE == 2) ? 64 : 1];
   __shared__ int s_idx[(MODE == 1 || MODE == 2) ? 64 : 1];
-  const int per_tile = a.sub_x * a.sub_y;
-  constexpr int RW = NB == 1 ? 8 : 16, RH = NB == 4 ? 16 : 8;  // the wave's pixel region: NB 8x8 sub-blocks
-  int tile, quad;
-  if (a.tile_order) {
-    const int b = blockIdx.x;
-    const int heavy = (NB > 1 && a.heavy) ? min(*a.heavy, a.heavy_cap) : 0;
-    if (NB > 1 && b < 4 * heavy) {
-      tile = a.tile_order[b >> 2];
-      int x0, y0, yout0;
-      tile_origin(a, tile, x0, y0, yout0);
-      x0 += (b & 1) * 8; y0 += ((b >> 1) & 1) * 8; yout0 += ((b >> 1) & 1) * 8;
-      if (x0 < a.W && y0 < a.H) raster_fwd_body<1, FP, MODE>(a, tile, x0, y0, yout0, s_geo, s_vis, s_idx);
-      return;
-    }
-    const int c = b - 4 * heavy, rank = heavy + c / per_tile;
-    if (rank >= a.num_tiles) return;
-    tile = a.tile_order[rank];
-    quad = c % per_tile;
-  } else {
-    const int item = gs_xcd_remap(blockIdx.x, a.num_items);
-    if (item < 0) return;
-    tile = item / per_tile;
-    quad = item - tile * per_tile;
-  }
-  int x0, y0, yout0;
-  tile_origin(a, tile, x0, y0, yout0);
-  x0 += (quad % a.sub_x) * RW; y0 += (quad / a.sub_x) * RH; yout0 += (quad / a.sub_x) * RH;
-  if (x0 >= a.W || y0 >= a.H) return;
-  raster_fwd_body<NB, FP, MODE>(a, tile, x0, y0, yout0, s_geo, s_vis, s_idx);
+  gs_raster_region<NB>(a, [&](auto nb, int tile, int x0, int y0, int yout0) {
+    raster_fwd_body<decltype(nb)::value, FP, MODE>(a, tile, x0, y0, yout0, s_geo, s_vis, s_idx);
+  });
 }
 
 template <int NB, int MODE>
 int launch_fp(const FwdArgs& a, hipStream_t s) {
-  const int grid = 8 * int(gs_div_up(a.num_items + (a.heavy ? 4 * a.heavy_cap : 0), 8));
+  const int grid = gs_raster_grid(a);
   if (MODE == 3 && a.F == 1) hipLaunchKernelGGL((raster_fwd_kernel<NB, 1, MODE>), dim3(grid), dim3(64), 0, s, a);
   else if (a.F <= 3) hipLaunchKernelGGL((raster_fwd_kernel<NB, 3, MODE>), dim3(grid), dim3(64), 0, s, a);
   else if (a.F <= 5) hipLaunchKernelGGL((raster_fwd_kernel<NB, 5, MODE>), dim3(grid), dim3(64), 0, s, a);
@@ -351,40 +275,21 @@ extern "C" int gs_raster_fwd(int64_t v, int32_t num_features, const float* point
   if (int rc = gs_check_background("gs_raster_fwd", cfg->use_alpha_blending, background != nullptr, background_offset,
                                    num_features))
     return rc;
-  GS_REQUIRE(width > 0 && height > 0, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd: image size %dx%d", width, height);
-  GS_REQUIRE(num_features >= 1 && num_features <= GS_MAX_FEATURES, GS_ERR_UNSUPPORTED,
-             "gs_raster_fwd: feature width %d not in [1,%d]", num_features, GS_MAX_FEATURES);
-  GS_REQUIRE(image && alpha && tile_ranges, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd: NULL output or ranges");
-  GS_REQUIRE(k == 0 || (points && features && overlap_to_point), GS_ERR_INVALID_ARGUMENT,
-             "gs_raster_fwd: NULL input with %lld overlaps", (long long)k);
+  if (int rc = gs_check_raster_call("gs_raster_fwd", width, height, num_features, GS_MAX_FEATURES)) return rc;
   const bool vis = cfg->compute_visibility || cfg->compute_point_heuristic;
-  GS_REQUIRE(!vis || visibility || v == 0, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd: visibility buffer is NULL");
-  const int ts = cfg->tile_size;
+  if (int rc = gs_check_raster_fwd_buffers("gs_raster_fwd", image, alpha, tile_ranges, k, points, features,
+                                           overlap_to_point, vis, visibility, v))
+    return rc;
   FwdArgs a;
   a.points = points; a.features = features; a.ranges = reinterpret_cast<const int2*>(tile_ranges);
   a.o2p = overlap_to_point; a.image = image; a.alpha = alpha; a.visibility = visibility;
   a.W = width; a.H = height; a.F = num_features;
-  a.tiles_wide = int(gs_div_up(width, ts));
-  a.tile_size = ts;
-  if (int rc = gs_make_shard(shard, int(gs_div_up(height, ts)), &a.sh)) return rc;
-  const int num_tiles = a.tiles_wide * a.sh.local_rows;
-  if (num_tiles == 0) return GS_OK;
-  const int nb = gs_raster_sub_blocks(cfg, num_tiles, 0);
-  a.sub_x = ts / (nb == 1 ? 8 : 16);
-  a.sub_y = ts / (nb == 4 ? 16 : 8);
-  a.num_items = num_tiles * a.sub_x * a.sub_y;
-  a.tile_order = tile_order;
-  a.num_tiles = num_tiles;
-  // the split needs the 2x2-quadrant geometry of a 16-pixel tile and a launch order to index into
-  a.heavy = (tile_order && ts == 16 && nb > 1) ? heavy_tiles : nullptr;
-  a.heavy_cap = num_tiles / 4;
-  if (cfg->tune_no_heavy_split) a.heavy = nullptr;
+  int nb = 0;
+  if (int rc = gs_raster_geometry(a, cfg, width, height, tile_order, heavy_tiles, shard, 0, nb)) return rc;
+  if (a.num_tiles == 0) return GS_OK;
   a.cmax = cfg->clamp_max_alpha; a.thr = cfg->alpha_threshold; a.inv_thr = 1.0f / cfg->alpha_threshold;
   a.sat_level = 1.0f - cfg->saturate_threshold;
-  // below 2^-25 (half an ulp of 1) the reference's own f32 accumulation W += w no longer changes W, but it still adds
-  // alpha * (1 - W) * feature for every remaining splat with 1 - W stuck at ~2^-24; this kernel carries T itself and
-  // stops here: forward_cut = 0 differs from the reference by < N * 2^-24 * max|feature| (N remaining splats)
-  a.cut = cfg->forward_cut > 2.98023223876953125e-08f ? cfg->forward_cut : 2.98023223876953125e-08f;
+  a.cut = gs_forward_cut(cfg);
   a.blend = cfg->use_alpha_blending; a.vis = vis; a.aa = cfg->antialias;
   a.bg = background; a.bg_off = background ? background_offset : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);

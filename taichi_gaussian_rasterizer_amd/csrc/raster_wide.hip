@@ -4,8 +4,8 @@
 //
 // The narrow kernels (raster_fwd.hip, raster_bwd.hip) hold a pixel's F channels in registers and blend them inside the
 // per-splat walk: at F > 32 that neither fits nor pays.  Here the walk and the channels are separated:
-//   * ONE wave64 per 8x8 pixel region, one pixel per lane; splats staged 64 at a time (geometry only), with the
-//     narrow kernels' sub-block mask and the general (MODE 2) per-pixel arithmetic, antialiased pdf included.
+//   * ONE wave64 per 8x8 pixel region, one pixel per lane; splats staged 64 at a time (geometry only) as the narrow
+//     kernels' general (MODE 2) records (raster_walk.h), with their per-pixel arithmetic (raster_pdf.h), antialias included.
 //   * Forward: the walk records the blend weights w[s][p] = alpha T in LDS; then, per 32-channel chunk of the staged
 //     splats' features (LDS), each lane adds sum_s w[s][p] f[s][c] for 4 pixels x 8 channels of the chunk straight
 //     into the image (the wave owns its pixels: a load-add-store, no atomics).  Visibility and alpha come from the
@@ -19,6 +19,7 @@
 
 #include "gs_common.h"
 #include "raster_pdf.h"
+#include "raster_walk.h"
 
 namespace {
 
@@ -50,19 +51,6 @@ struct WideArgs {
   int blend, vis, aa, heur_on;
 };
 
-// block -> the region's first pixel; false for a padding block or a region outside the image
-__device__ __forceinline__ bool wide_region(const WideArgs& a, int& tile, int& x0, int& y0) {
-  const int item = gs_xcd_remap(blockIdx.x, a.num_items);
-  if (item < 0) return false;
-  const int per_tile = a.side * a.side;
-  tile = item / per_tile;
-  const int q = item - tile * per_tile;
-  const int ty = tile / a.tiles_wide;
-  x0 = (tile - ty * a.tiles_wide) * a.tile_size + (q % a.side) * 8;
-  y0 = ty * a.tile_size + (q / a.side) * 8;
-  return x0 < a.W && y0 < a.H;
-}
-
 // Stage channels [k0, k0 + 32) of 64 rows into an LDS chunk: row r comes from src + row_off(r) (a negative offset
 // gives a zero row).  Lane (c = lane & 31, r0 = lane >> 5) loads column c of rows r0, r0 + 2, ...: all 32 loads of a
 // lane are issued before the first is waited for (a loop that waits per row exposes one memory latency per row).
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(64) void raster_fwd_wide_kernel(const WideArgs a) {
   __shared__ float s_vis[64];
   __shared__ int s_idx[64];
   int tile, x0, y0;
-  if (!wide_region(a, tile, x0, y0)) return;
+  if (!gs_wide_region(a, tile, x0, y0)) return;
   const int lane = threadIdx.x;
   const int X = x0 + (lane & 7), Y = y0 + (lane >> 3);
   const bool inb = X < a.W && Y < a.H;
@@ -110,7 +98,6 @@ __global__ __launch_bounds__(64) void raster_fwd_wide_kernel(const WideArgs a) {
 
   const int2 range_v = a.ranges[tile];
   const int range_x = __builtin_amdgcn_readfirstlane(range_v.x), range_y = __builtin_amdgcn_readfirstlane(range_v.y);
-  const float k_exp = 0.84932180028801904f;  // sqrt(0.5 * log2(e))
   for (int g0 = range_x; g0 < range_y; g0 += 64) {
     // the early stops of raster_fwd.hip: forward_cut while blending, every pixel done in quantile mode
     const bool open = a.blend ? Tr > a.cut : (inb && !done);
@@ -119,20 +106,8 @@ __global__ __launch_bounds__(64) void raster_fwd_wide_kernel(const WideArgs a) {
     int staged = 0;
     if (lane < cnt) {
       const int idx = a.o2p[g0 + lane];
-      const float* p = a.points + int64_t(idx) * 7;
-      const float mx = p[0], my = p[1], ax = p[2], ay = p[3], sx = p[4], sy = p[5], al = p[6];
-      const float isx = gs_rcp_fast(sx), isy = gs_rcp_fast(sy);
-      const float Ax = ax * isx * k_exp, Ay = ay * isx * k_exp, Bx = -ay * isy * k_exp, By = ax * isy * k_exp;
-      if (a.aa)
-        staged = gs_sub_block_mask_antialias<1>(ax, ay, sx, sy, al, a.inv_thr, s_sig(0.5f, isx) - s_sig(-0.5f, isx),
-                                                s_sig(0.5f, isy) - s_sig(-0.5f, isy), float(x0) + 0.5f - mx,
-                                                float(y0) + 0.5f - my);
-      else if (al > a.thr)
-        staged = gs_sub_block_mask<1>(Ax, Ay, Bx, By, __log2f(al * a.inv_thr), float(x0) + 0.5f - mx,
-                                      float(y0) + 0.5f - my);
-      s_geo[lane][0] = make_float4(mx, my, Ax, Ay);
-      s_geo[lane][1] = make_float4(Bx, By, al, 0.0f);
-      s_geo[lane][2] = make_float4(ax, ay, isx, isy);
+      const GsSplat sp = gs_load_splat(a.points + int64_t(idx) * 7);
+      staged = gs_stage_general<1, false>(s_geo[lane], sp, x0, y0, a.thr, a.inv_thr, a.aa, false);
       s_idx[lane] = idx;
       s_vis[lane] = 0.0f;
     }
@@ -142,18 +117,7 @@ __global__ __launch_bounds__(64) void raster_fwd_wide_kernel(const WideArgs a) {
     for (uint64_t m = reach; m != 0ull; m &= m - 1ull) {
       const int j = __builtin_ctzll(m);
       const float4 g0v = s_geo[j][0], g1v = s_geo[j][1], g2v = s_geo[j][2];
-      const float dx = Xf - g0v.x, dy = Yf - g0v.y;
-      float alpha;
-      if (a.aa) {  // raster_fwd.hip MODE 2
-        const float tx = dx * g2v.x + dy * g2v.y, ty = dy * g2v.x - dx * g2v.y;
-        float nx, dnx, ny, dny;
-        aa_axis(tx, g2v.z, nx, dnx);
-        aa_axis(ty, g2v.w, ny, dny);
-        alpha = g1v.z * (6.28318530717958648f * nx * ny * gs_rcp_fast(dnx * dny * g2v.z * g2v.w));
-      } else {
-        const float tx = dx * g0v.z + dy * g0v.w, ty = dx * g1v.x + dy * g1v.y;
-        alpha = g1v.z * gs_exp2_fast(-(tx * tx + ty * ty));
-      }
+      const float alpha = gs_general_alpha(a.aa, Xf - g0v.x, Yf - g0v.y, g0v, g1v, g2v);
       const float al = __builtin_amdgcn_fmed3f(alpha, a.cmax, -1.0f);  // min(alpha, cmax) (forward.py:98-99)
       const bool hit = al > a.thr && !done;
       const float w = (hit ? al : 0.0f) * Tr;
@@ -242,7 +206,7 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
   __shared__ int s_idx[64];
   float(*s_acc)[9] = reinterpret_cast<float(*)[9]>(&s_f[0][0]);
   int tile, x0, y0;
-  if (!wide_region(a, tile, x0, y0)) return;
+  if (!gs_wide_region(a, tile, x0, y0)) return;
   const int lane = threadIdx.x;
   const int X = x0 + (lane & 7), Y = y0 + (lane >> 3);
   const bool inb = X < a.W && Y < a.H;
@@ -283,28 +247,10 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
     if (__ballot(Tr > a.tsat) == 0ull) break;  // every pixel saturated (backward.py:116-118)
     const int cnt = __builtin_amdgcn_readfirstlane(min(64, range_y - g0));
     int staged = 0;
-    if (lane < cnt) {  // raster_bwd.hip MODE 2 records
+    if (lane < cnt) {
       const int idx = a.o2p[g0 + lane];
-      const float* p = a.points + int64_t(idx) * 7;
-      const float mx = p[0], my = p[1], ax = p[2], ay = p[3], al = p[6];
-      const float isx = gs_rcp_fast(p[4]), isy = gs_rcp_fast(p[5]);
-      const float Ax = ax * isx, Ay = ay * isx, Bx = -ay * isy, By = ax * isy;
-      if (a.aa) {
-        float s1, s2, u0, u1;
-        s_sig_grad(0.5f, isx, s1, u0, u1);
-        s_sig_grad(0.5f, isy, s2, u0, u1);
-        staged = gs_sub_block_mask_antialias<1>(ax, ay, p[4], p[5], al, a.inv_thr, 2.0f * s1 - 1.0f, 2.0f * s2 - 1.0f,
-                                                float(x0) + 0.5f - mx, float(y0) + 0.5f - my);
-        s_geo[lane][0] = make_float4(mx, my, p[4], p[5]);
-        s_geo[lane][1] = make_float4(0.5f * isx, 0.5f * isy, al, 0.0f);
-      } else {
-        if (al > a.thr)
-          staged = gs_sub_block_mask<1>(Ax, Ay, Bx, By, __log2f(al * a.inv_thr) * 1.38629436111989f,
-                                        float(x0) + 0.5f - mx, float(y0) + 0.5f - my);
-        s_geo[lane][0] = make_float4(mx, my, Ax, Ay);
-        s_geo[lane][1] = make_float4(Bx, By, al, 0.0f);
-      }
-      s_geo[lane][2] = make_float4(ax, ay, isx, isy);
+      const GsSplat sp = gs_load_splat(a.points + int64_t(idx) * 7);
+      staged = gs_stage_general<1, true>(s_geo[lane], sp, x0, y0, a.thr, a.inv_thr, a.aa, false);
       s_idx[lane] = idx;
     }
     const uint64_t reach = __ballot(staged & 1);
@@ -350,7 +296,7 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
     for (int c = 0; c < 9; ++c) s_acc[lane][c] = 0.0f;
     __syncthreads();
 
-    // ---- the walk (raster_bwd.hip MODE 2 with d = D[s][p] for f . g); D[j][p] becomes w[j][p]
+    // ---- the walk (the narrow MODE 2 arithmetic, raster_pdf.h, with d = D[s][p] for f . g); D[j][p] becomes w[j][p]
     for (int j = 0; j < cnt; ++j) {
       if (!((reach >> j) & 1ull)) {
         s_dw[j][lane] = 0.0f;
@@ -362,6 +308,7 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
       float p, dmx = 0, dmy = 0, dax = 0, day = 0, dsx = 0, dsy = 0, Px = 0, Py = 0;
       float aa_z[4] = {0, 0, 0, 0}, aa_a[4] = {0, 0, 0, 0};
       if (a.aa) {
+        // the antialiased pdf's value half, written out as in raster_bwd.hip (raster_pdf.h says why, and what it is)
         const float ux = dx * g2v.x + dy * g2v.y, uy = dy * g2v.x - dx * g2v.y;
         aa_z[0] = __builtin_fmaf(ux, g2v.z, g1v.x); aa_z[1] = __builtin_fmaf(ux, g2v.z, -g1v.x);
         aa_z[2] = __builtin_fmaf(uy, g2v.w, g1v.y); aa_z[3] = __builtin_fmaf(uy, g2v.w, -g1v.y);
@@ -369,50 +316,20 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
         for (int k = 0; k < 4; ++k) aa_a[k] = s_sig_value(aa_z[k]);
         p = 6.28318530717958648f * (g0v.z * (aa_a[0] - aa_a[1])) * (g0v.w * (aa_a[2] - aa_a[3]));
       } else {
-        const float tx = dx * g0v.z + dy * g0v.w, ty = dx * g1v.x + dy * g1v.y;
-        p = gs_exp2_fast(-0.72134752044448170f * (tx * tx + ty * ty));
-        const float txs = tx * g2v.z, tys = ty * g2v.w;  // taichi_lib/generic.py:321-336
-        dsx = tx * tx * p * g2v.z;
-        dsy = ty * ty * p * g2v.w;
-        dax = p * (txs * -dx + tys * -dy);
-        day = p * (txs * -dy + tys * dx);
-        dmx = p * (txs * g2v.x - tys * g2v.y);
-        dmy = p * (txs * g2v.y + tys * g2v.x);
+        float tx, ty;
+        p = gs_general_pdf_plain(dx, dy, g0v, g1v, g2v, tx, ty, dmx, dmy, dax, day, dsx, dsy);
       }
       const float alpha_raw = g1v.z * p;
       const bool hit = alpha_raw > a.thr && Tr > a.tsat;  // backward.py:160,166
       float v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       float w = 0.0f;
       if (hit) {
-        if (a.aa) {
-          const float d0 = s_sig_slope(aa_z[0], aa_a[0]), d1 = s_sig_slope(aa_z[1], aa_a[1]);
-          const float d2 = s_sig_slope(aa_z[2], aa_a[2]), d3 = s_sig_slope(aa_z[3], aa_a[3]);
-          const float Dx = aa_a[0] - aa_a[1], Dy = aa_a[2] - aa_a[3];
-          const float fxt = 6.28318530717958648f * (g0v.z * Dx), fyt = 6.28318530717958648f * (g0v.w * Dy);
-          Px = (d0 - d1) * fyt;
-          Py = fxt * (d2 - d3);
-          dsx = (Dx - __builtin_fmaf(aa_z[0], d0, -(aa_z[1] * d1))) * fyt;
-          dsy = fxt * (Dy - __builtin_fmaf(aa_z[2], d2, -(aa_z[3] * d3)));
-          dax = __builtin_fmaf(Px, dx, Py * dy);
-          day = __builtin_fmaf(Px, dy, -(Py * dx));
-        }
+        if (a.aa) gs_general_pdf_gradient(dx, dy, g0v, aa_z, aa_a, Px, Py, dax, day, dsx, dsy);
         const float alc = __builtin_amdgcn_fmed3f(alpha_raw, a.cmax, -1.0f);  // min(alpha, cmax) (:169)
         w = alc * Tr;
         // dL/dalpha = (T d - R) / (1 - alpha), R still including this splat's share (:180-182)
         const float alpha_grad = (Tr * d - R) * gs_rcp_fast(1.0f - alc);
-        const float aag = g1v.z * alpha_grad;  // :184
-        if (a.aa) {
-          v[0] = aag * Px; v[1] = aag * Py;  // splat frame; rotated in the epilogue
-          dmx = -Px * g2v.x + Py * g2v.y;
-          dmy = -Px * g2v.y - Py * g2v.x;
-        } else {
-          v[0] = aag * dmx; v[1] = aag * dmy;
-        }
-        v[2] = aag * dax; v[3] = aag * day;
-        v[4] = aag * dsx; v[5] = aag * dsy;
-        v[6] = p * alpha_grad;
-        v[7] = aag * aag;  // :194-198
-        v[8] = fabsf(aag * dmx) + fabsf(aag * dmy);
+        gs_general_sums<false>(a.aa, 1, g1v, g2v, p, dmx, dmy, dax, day, dsx, dsy, Px, Py, alpha_grad, v);
         Tr = __builtin_fmaf(-Tr, alc, Tr);
         R = __builtin_fmaf(-d, w, R);
       }
@@ -431,8 +348,7 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
       for (int c = 0; c < 9; ++c) t[c] = s_acc[lane][c];
       if (a.aa) {  // the mean's gradient out of the splat frame
         const float ax = s_geo[lane][2].x, ay = s_geo[lane][2].y;
-        const float m0 = -t[0] * ax + t[1] * ay, m1 = -t[0] * ay - t[1] * ax;
-        t[0] = m0; t[1] = m1;
+        gs_mean_grad_from_splat_frame(t[0], t[1], ax, ay);
       }
       const int64_t idx = s_idx[lane];
 #pragma unroll
@@ -485,9 +401,7 @@ __global__ __launch_bounds__(64) void raster_bwd_wide_kernel(const WideArgs a) {
 int wide_setup(const char* what, int32_t num_features, int32_t width, int32_t height, const GsRasterConfig* cfg,
                WideArgs& a) {
   if (int rc = gs_check_cfg(cfg)) return rc;
-  GS_REQUIRE(width > 0 && height > 0, GS_ERR_INVALID_ARGUMENT, "%s: image size %dx%d", what, width, height);
-  GS_REQUIRE(num_features >= 1 && num_features <= GS_MAX_WIDE_FEATURES, GS_ERR_UNSUPPORTED,
-             "%s: feature width %d not in [1,%d]", what, num_features, GS_MAX_WIDE_FEATURES);
+  if (int rc = gs_check_raster_call(what, width, height, num_features, GS_MAX_WIDE_FEATURES)) return rc;
   a = WideArgs{};
   const int ts = cfg->tile_size;
   a.W = width; a.H = height; a.F = num_features;
@@ -498,8 +412,7 @@ int wide_setup(const char* what, int32_t num_features, int32_t width, int32_t he
   a.cmax = cfg->clamp_max_alpha; a.thr = cfg->alpha_threshold; a.inv_thr = 1.0f / cfg->alpha_threshold;
   a.sat_level = 1.0f - cfg->saturate_threshold;
   a.tsat = 1.0f - cfg->saturate_threshold;
-  // gs_raster_fwd: forward_cut = 0 acts as 2^-25
-  a.cut = cfg->forward_cut > 2.98023223876953125e-08f ? cfg->forward_cut : 2.98023223876953125e-08f;
+  a.cut = gs_forward_cut(cfg);
   a.blend = cfg->use_alpha_blending; a.aa = cfg->antialias;
   a.vis = cfg->compute_visibility || cfg->compute_point_heuristic;
   a.heur_on = cfg->compute_point_heuristic;
@@ -519,10 +432,9 @@ extern "C" int gs_raster_fwd_wide(int64_t v, int32_t num_features, const float* 
                                    background_offset, num_features))
     return rc;
   a.bg = background; a.bg_off = background ? background_offset : 0;
-  GS_REQUIRE(image && alpha && tile_ranges, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd_wide: NULL output or ranges");
-  GS_REQUIRE(k == 0 || (points && features && overlap_to_point), GS_ERR_INVALID_ARGUMENT,
-             "gs_raster_fwd_wide: NULL input with %lld overlaps", (long long)k);
-  GS_REQUIRE(!a.vis || visibility || v == 0, GS_ERR_INVALID_ARGUMENT, "gs_raster_fwd_wide: visibility buffer is NULL");
+  if (int rc = gs_check_raster_fwd_buffers("gs_raster_fwd_wide", image, alpha, tile_ranges, k, points, features,
+                                           overlap_to_point, a.vis != 0, visibility, v))
+    return rc;
   a.points = points; a.features = features; a.ranges = reinterpret_cast<const int2*>(tile_ranges);
   a.o2p = overlap_to_point; a.out_image = image; a.alpha = alpha; a.visibility = visibility;
   if (v == 0) a.vis = 0;
