@@ -31,6 +31,13 @@ void gs_set_error(const char* fmt, ...);
 static inline int64_t gs_div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t gs_align_up(int64_t a, int64_t b) { return gs_div_up(a, b) * b; }
 
+// clear `bytes` of device memory on the stream; `what` is the whole message of the failure
+static inline int gs_memset_async(void* ptr, size_t bytes, hipStream_t stream, const char* what) {
+  if (hipMemsetAsync(ptr, 0, bytes, stream) == hipSuccess) return GS_OK;
+  gs_set_error("%s", what);
+  return GS_ERR_LAUNCH;
+}
+
 static inline int gs_check_cfg(const GsRasterConfig* cfg) {
   GS_REQUIRE(cfg != nullptr, GS_ERR_INVALID_ARGUMENT, "config is NULL");
   GS_REQUIRE(cfg->tile_size == 8 || cfg->tile_size == 16 || cfg->tile_size == 32, GS_ERR_UNSUPPORTED,
@@ -176,6 +183,10 @@ int gs_map_prepare_ex(int64_t v, const int32_t* v_dev, const float* points, int3
                       const GsRasterConfig* cfg, int64_t k_capacity, int32_t* tile_ranges, int32_t* counts_out,
                       int32_t* counts_host, int32_t* tile_order, const GsRowShard* shard, void* scratch,
                       int64_t scratch_bytes, int binned, void* stream);
+// the sort launches behind gs_map_finish (tile_sort.hip): every tile's bucket of `pairs` (depth key << 32 | index) by
+// ascending composite -> overlap_to_point and, optionally, the sorted keys.  max_tile_count as gs_map_finish takes it.
+int gs_map_sort_tiles(int num_tiles, const int32_t* tile_ranges, uint64_t* pairs, int32_t* overlap_to_point,
+                      uint64_t* sorted_keys, int32_t use_depth16, int32_t max_tile_count, hipStream_t stream);
 // rows[i, 0..7) += add_points[i, 0..7) and rows[i, depth_col] += add_depth[i] for i < v (either may be NULL)
 int gs_rows_add(int64_t v, int32_t row_floats, float* rows, const float* add_points, const float* add_depth,
                 int32_t depth_col, void* stream);
@@ -339,6 +350,66 @@ __device__ __forceinline__ float gs_wave_reduce_transposed<9>(float (&v)[9], int
   x = gs_dpp_add_full<0x143>(x);  // row_bcast:31: rows 2, 3 add (row 0 + row 1) -> row 3 holds the total
   const float d = gs_wave_reduce_transposed<8>(w, lane);
   return lane == 60 ? x : d;
+}
+
+// Stable compaction of one flag per thread over workgroups of WAVES waves: ballot, per-wave popcount, slot = the
+// flagged rows of the workgroups in front + of the waves in front + of the lower lanes.  The rows in front of the
+// workgroup come from `offset` (its entry of a precomputed exclusive prefix) or, when that is NULL, from the workgroup
+// summing block_counts[0 .. blocks_before) itself.  The same call by every thread of the workgroup (one barrier).
+struct GsCompactSlot {
+  int first;  // slot of the workgroup's first flagged row
+  int slot;   // slot of this thread's row (meaningful when its flag is set)
+  int total;  // flagged rows of the workgroup
+};
+template <int WAVES>
+__device__ __forceinline__ GsCompactSlot gs_stable_compact(bool flag, const int* offset, const int* block_counts,
+                                                           int blocks_before) {
+  __shared__ int s_cnt[WAVES];
+  __shared__ int s_before[WAVES];
+  const uint64_t b = __ballot(flag);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) s_cnt[wave] = __popcll(b);
+  if (!offset) {
+    int before = 0;
+    for (int j = threadIdx.x; j < blocks_before; j += WAVES * 64) before += block_counts[j];
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+    if (lane == 0) s_before[wave] = before;
+  }
+  __syncthreads();
+  GsCompactSlot c;
+  c.first = 0;
+  if (offset) {
+    c.first = *offset;
+  } else {
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) c.first += s_before[w];
+  }
+  int base = c.first;
+  c.total = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    base += w < wave ? s_cnt[w] : 0;
+    c.total += s_cnt[w];
+  }
+  c.slot = base + __popcll(b & ((1ull << lane) - 1ull));
+  return c;
+}
+
+// one compact row of the projection's outputs from its staged pair (r0, r1) (project.hip stages them; r1.w = depth)
+__device__ __forceinline__ void gs_write_compact_row(const GsCompactArgs& c, int slot, int64_t i, const float4& r0,
+                                                     const float4& r1) {
+  float* p = c.points + int64_t(slot) * 7;
+  p[0] = r0.x; p[1] = r0.y; p[2] = r0.z; p[3] = r0.w; p[4] = r1.x; p[5] = r1.y; p[6] = r1.z;
+  c.depth[slot] = r1.w;
+  if (c.depth_feat) {  // renderer.py:191-193: raster features [z, z^2, ...]
+    c.depth_feat[int64_t(slot) * c.depth_feat_stride] = r1.w;
+    c.depth_feat[int64_t(slot) * c.depth_feat_stride + 1] = r1.w * r1.w;
+  }
+  // fixed f32 op order: the sort key is the bit pattern of this value.  No multiply feeds an add here,
+  // so the bits are the same with and without -ffp-contract=off (project.hip and mapper.hip differ in it).
+  const float inv_d = __fdiv_rn(1.0f, r1.w);
+  c.ndc[slot] = 1.0f - __fdiv_rn(inv_d - c.inv_far, c.ndc_denom);
+  c.indexes[slot] = i;
 }
 
 __device__ __forceinline__ float gs_exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32

@@ -49,62 +49,30 @@ __global__ __launch_bounds__(256) void project_kernel(ProjArgs a, float4* st_row
 // pass 2: stable compaction
 // block_offsets == nullptr: every workgroup sums the visible counts of the workgroups before it itself
 // (block_counts, a few KB that stay in L2) instead of reading a prefix computed by three scan launches
-__global__ __launch_bounds__(256) void compact_kernel(int64_t n, const float4* st_rows, const int* block_offsets,
-                                                      const int* block_counts, int num_blocks, float inv_far, float ndc_denom, float* points,
-                                                      float* depth, float* ndc, int64_t* indexes, int* slot_of,
-                                                      int* num_visible, float* depth_feat, int depth_feat_stride,
-                                                      float4* zero_rows, int zero_row_v4) {
-  __shared__ int s_cnt[4];
-  __shared__ int s_before[4];
+__global__ __launch_bounds__(256) void compact_kernel(GsCompactArgs c) {
   const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const float4* st_rows = static_cast<const float4*>(c.st_rows);
   float4 r0 = make_float4(0, 0, 0, 0), r1 = r0;
   bool vis = false;
-  if (i < n) {
+  if (i < c.n) {
     r0 = st_rows[2 * i];
     r1 = st_rows[2 * i + 1];
     vis = r1.w != 0.0f;
   }
-  const uint64_t b = __ballot(vis);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) s_cnt[wave] = __popcll(b);
-  int before = 0;
-  if (!block_offsets) {
-    for (int j = threadIdx.x; j < int(blockIdx.x); j += 256) before += block_counts[j];
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
-    if (lane == 0) s_before[wave] = before;
-  }
-  __syncthreads();
-  int base = block_offsets ? block_offsets[blockIdx.x] : s_before[0] + s_before[1] + s_before[2] + s_before[3];
-  const int block_start = base;
-  for (int w = 0; w < wave; ++w) base += s_cnt[w];
-  if (i < n) {
-    int slot = -1;
-    if (vis) {
-      slot = base + __popcll(b & ((1ull << lane) - 1ull));
-      float* p = points + int64_t(slot) * 7;
-      p[0] = r0.x; p[1] = r0.y; p[2] = r0.z; p[3] = r0.w; p[4] = r1.x; p[5] = r1.y; p[6] = r1.z;
-      depth[slot] = r1.w;
-      if (depth_feat) {  // renderer.py:191-193: raster features [z, z^2, ...]
-        depth_feat[int64_t(slot) * depth_feat_stride] = r1.w;
-        depth_feat[int64_t(slot) * depth_feat_stride + 1] = r1.w * r1.w;
-      }
-      // fixed f32 op order: the sort key is the bit pattern of this value
-      const float inv_d = __fdiv_rn(1.0f, r1.w);
-      ndc[slot] = 1.0f - __fdiv_rn(inv_d - inv_far, ndc_denom);
-      indexes[slot] = i;
-    }
-    slot_of[i] = slot;
+  const GsCompactSlot k = gs_stable_compact<4>(vis, c.block_offsets ? c.block_offsets + blockIdx.x : nullptr,
+                                               c.block_counts, int(blockIdx.x));
+  if (i < c.n) {
+    if (vis) gs_write_compact_row(c, k.slot, i, r0, r1);
+    c.slot_of[i] = vis ? k.slot : -1;
   }
   // the frame's gradient rows (gs_raster_bwd accumulates into them with atomics): zero-filled here, by the pass that
   // already streams the V compact rows, instead of by a fill launch in front of the backward.  The workgroup's rows are
   // one contiguous range, cleared with consecutive 16-byte stores (a lane clearing its own 64-byte row costs 12 us more)
-  if (zero_rows) {
-    const int mine = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    float4* dst = zero_rows + int64_t(block_start) * zero_row_v4;
-    for (int e = threadIdx.x; e < mine * zero_row_v4; e += 256) dst[e] = make_float4(0, 0, 0, 0);
+  if (c.zero_rows) {
+    float4* dst = static_cast<float4*>(c.zero_rows) + int64_t(k.first) * c.zero_row_v4;
+    for (int e = threadIdx.x; e < k.total * c.zero_row_v4; e += 256) dst[e] = make_float4(0, 0, 0, 0);
   }
-  if (int(blockIdx.x) == num_blocks - 1 && threadIdx.x == 0)
-    *num_visible = block_start + s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+  if (int(blockIdx.x) == c.num_blocks - 1 && threadIdx.x == 0) *c.num_visible = k.first + k.total;
 }
 
 // ------------------------------------------------------------------------------- backward
@@ -273,18 +241,14 @@ int gs_project_fwd_ex(int64_t n, const float* position, const float* log_scaling
   const bool self_offsets = nb <= 16384;
   if (!self_offsets)
     if (int rc = gs_full_cumsum_i32(nb, counts, offsets, scan_scratch, gs_cumsum_scratch_bytes(nb), s)) return rc;
-  if (bin) {
-    GsCompactArgs c;
-    c.n = n; c.st_rows = st_rows; c.block_offsets = self_offsets ? nullptr : offsets; c.block_counts = counts;
-    c.num_blocks = nb; c.inv_far = a.inv_far; c.ndc_denom = a.ndc_denom;
-    c.points = points; c.depth = depth; c.ndc = ndc_depth; c.indexes = indexes; c.slot_of = slot_of;
-    c.num_visible = num_visible; c.depth_feat = depth_features; c.depth_feat_stride = depth_features_stride;
-    c.zero_rows = zero_rows; c.zero_row_v4 = zero_row_floats / 4;
-    return gs_map_compact_bin(bin, &c, stream);
-  }
-  hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(256), 0, s, n, st_rows, self_offsets ? nullptr : offsets, counts, nb, a.inv_far, a.ndc_denom,
-                     points, depth, ndc_depth, indexes, slot_of, num_visible, depth_features, depth_features_stride,
-                     reinterpret_cast<float4*>(zero_rows), zero_row_floats / 4);
+  GsCompactArgs c;
+  c.n = n; c.st_rows = st_rows; c.block_offsets = self_offsets ? nullptr : offsets; c.block_counts = counts;
+  c.num_blocks = nb; c.inv_far = a.inv_far; c.ndc_denom = a.ndc_denom;
+  c.points = points; c.depth = depth; c.ndc = ndc_depth; c.indexes = indexes; c.slot_of = slot_of;
+  c.num_visible = num_visible; c.depth_feat = depth_features; c.depth_feat_stride = depth_features_stride;
+  c.zero_rows = zero_rows; c.zero_row_v4 = zero_row_floats / 4;
+  if (bin) return gs_map_compact_bin(bin, &c, stream);
+  hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(256), 0, s, c);
   GS_CHECK_LAUNCH("gs_project_fwd/compact");
   return GS_OK;
 }

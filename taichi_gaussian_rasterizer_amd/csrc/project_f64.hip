@@ -39,19 +39,13 @@ __global__ __launch_bounds__(256) void compact_f64_kernel(int64_t n, int nb, con
                                                           const int32_t* flags, const int32_t* offsets, double inv_far,
                                                           double ndc_denom, double* points, double* depth, double* ndc,
                                                           int64_t* indexes, int32_t* slot_of, int32_t* num_visible) {
-  __shared__ int32_t s_cnt[4];
   const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
   const bool vis = i < n && flags[i] != 0;
-  const uint64_t b = __ballot(vis);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) s_cnt[wave] = __popcll(b);
-  __syncthreads();
-  int base = offsets[blockIdx.x];
-  for (int w = 0; w < wave; ++w) base += s_cnt[w];
+  const GsCompactSlot cs = gs_stable_compact<4>(vis, offsets + blockIdx.x, nullptr, 0);
   if (i < n) {
     int slot = -1;
     if (vis) {
-      slot = base + __popcll(b & ((1ull << lane) - 1ull));
+      slot = cs.slot;
       const double* r = st_rows + 8 * i;
       for (int k = 0; k < 7; ++k) points[int64_t(slot) * 7 + k] = r[k];
       depth[slot] = r[7];

@@ -108,7 +108,7 @@ int sort_impl(int64_t k, const K* keys_in, const int* values_in, K* keys_out, in
     K* dst_k = to_out ? keys_out : tmp_keys;
     int* dst_v = to_out ? values_out : tmp_vals;
     hipLaunchKernelGGL((rs_hist<K>), dim3(blocks), dim3(256), 0, s, k, src_k, shift, bits, num_waves, hist);
-    // exclusive scan of the digit-major table, in place (multi-block scan of mapper.hip)
+    // exclusive scan of the digit-major table, in place (multi-block scan of map_reference.hip)
     if (int rc = gs_full_cumsum_i32(hist_n, hist, hist, scan_scratch, gs_cumsum_scratch_bytes(hist_n), s)) return rc;
     hipLaunchKernelGGL((rs_scatter<K>), dim3(blocks), dim3(256), 0, s, k, src_k, src_v, dst_k, dst_v, shift, bits,
                        num_waves, hist);

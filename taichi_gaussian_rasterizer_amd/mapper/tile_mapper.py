@@ -4,7 +4,7 @@ Operator interface of the reference mapper/tile_mapper.py:202-223:
 map_to_tiles(gaussians (V,7), depth (V,1), image_size (W,H), config, use_depth16=False)
   -> (overlap_to_point (K) int32, tile_ranges (Th,Tw,2) int32).
 
-Runs the fused per-tile pipeline of csrc/mapper.hip (histogram -> scan -> bucket -> per-tile sort)
+Runs the fused per-tile pipeline of csrc/mapper.hip and csrc/tile_sort.hip (histogram -> scan -> bucket -> per-tile sort)
 with ONE host read-back (K and the largest tile population).  `map_to_tiles_reference_stages`
 runs the reference's own stage sequence (count -> cumsum -> keys -> global radix sort -> ranges)
 on the reference-shaped primitives; both produce identical results.

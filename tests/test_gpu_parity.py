@@ -62,6 +62,74 @@ def test_mapper_crowded_tile(n):
     assert (pu.to_np(ranges) == ranges_ref).all() and (pu.to_np(o2p) == o2p_ref).all()
 
 
+def _region_count(tiles_x, tiles_y):
+    """the mapper's region grid (csrc/mapper.hip: make_grid): the smallest power-of-two edge >= 8 tiles that keeps the
+    region count <= 1024"""
+    edge = 8
+    while -(-tiles_x // edge) * -(-tiles_y // edge) > 1024:
+        edge *= 2
+    return -(-tiles_x // edge) * -(-tiles_y // edge)
+
+
+def test_mapper_scan_path_binning_at_its_smallest_size():
+    """The binning pass reserves its places with returning atomics up to 2^16 (workgroup, region) pairs and with the two
+    scan launches (region_part_scan_kernel, region_scan_kernel) beyond: 65 workgroups of 1024 Gaussians x 1024 regions is
+    the smallest standalone call that takes the scans."""
+    tile, size, n = 8, (2048, 2048), 64 * 1024 + 1
+    regions = _region_count(size[0] // tile, size[1] // tile)
+    assert regions == 1024 and -(-n // 1024) * regions > 65536
+    rng = np.random.default_rng(3)
+    mean = rng.uniform(0.0, 1.0, (n, 2)) * np.array(size, np.float64)
+    angle = rng.uniform(0.0, 2.0 * np.pi, n)
+    sigma = rng.uniform(0.5, 3.0, (n, 2))
+    alpha = rng.uniform(0.05, 0.9, (n, 1))
+    g2d = np.concatenate([mean, np.cos(angle)[:, None], np.sin(angle)[:, None], sigma, alpha], 1).astype(np.float32)
+    depth = rng.random((n, 1)).astype(np.float32)
+    cfg = RasterConfig(tile_size=tile)
+    o2p_ref, ranges_ref = orc.map_to_tiles(g2d, depth, size, orc.OracleConfig.of(cfg))
+    o2p, ranges = gs.map_to_tiles(dev(g2d), dev(depth), size, cfg)
+    assert (pu.to_np(ranges) == ranges_ref).all(), "tile ranges differ"
+    assert (pu.to_np(o2p) == o2p_ref).all(), "overlap order differs"
+
+
+@pytest.mark.parametrize("depth16", [False, True])
+@pytest.mark.parametrize("lo,step", [(40, 6), (40, 15)])
+def test_mapper_clustered_depths_through_every_row_count(lo, step, depth16):
+    """Tile t of a 8 x 4 grid holds exactly lo + step t splats, on three depth values: the wave sort's bucket sort gives
+    up on a bin of more than 40 keys (tile_sort.hip: BIN_LIMIT) and the rank sort runs, at every row count (64 keys per
+    row) of tile_rank_sort_kernel<4> ((40, 6): up to 226 splats) and <8> ((40, 15): up to 505).  Ties come out in
+    ascending Gaussian index."""
+    tile, size, tiles_x, num_tiles = 16, (128, 64), 8, 32
+    counts = lo + step * np.arange(num_tiles)
+    n = int(counts.sum())
+    rng = np.random.default_rng(11)
+    t = np.repeat(np.arange(num_tiles), counts)
+    origin = np.stack([(t % tiles_x) * tile, (t // tiles_x) * tile], 1).astype(np.float64)
+    mean = origin + 5.0 + 6.0 * rng.random((n, 2))
+    alpha = rng.uniform(0.3, 0.9, (n, 1))
+    depth = rng.choice(np.array([0.25, 0.5, 0.75], np.float32), (n, 1))
+    g2d = np.concatenate([mean, np.tile([1.0, 0.0], (n, 1)), np.full((n, 2), 0.4), alpha], 1).astype(np.float32)
+    perm = rng.permutation(n)  # index order is not tile order
+    g2d, depth = g2d[perm], depth[perm]
+    cfg = RasterConfig(tile_size=tile)
+    o2p_ref, ranges_ref, keys_ref = orc.map_to_tiles(g2d, depth, size, orc.OracleConfig.of(cfg), depth16,
+                                                     return_keys=True)
+    flat = ranges_ref.reshape(num_tiles, 2)
+    assert (flat[:, 1] - flat[:, 0] == counts).all(), "the layout's tile populations"
+    most_shared = {}  # row count -> most entries on one depth value in some tile of that row count
+    for a, b in flat:
+        rows = -(-int(b - a) // 64)
+        shared = int(np.unique(depth[o2p_ref[a:b], 0], return_counts=True)[1].max())
+        most_shared[rows] = max(most_shared.get(rows, 0), shared)
+    max_rows = -(-int(counts.max()) // 64)
+    assert max_rows == (4 if step == 6 else 8)
+    assert all(most_shared[rows] > 40 for rows in range(2, max_rows + 1)), most_shared
+    o2p, ranges, keys = gs.map_to_tiles(dev(g2d), dev(depth), size, cfg, use_depth16=depth16, return_keys=True)
+    assert (pu.to_np(ranges) == ranges_ref).all(), "tile ranges differ"
+    assert (pu.to_np(o2p) == o2p_ref).all(), "overlap order differs"
+    assert (pu.to_np(keys).view(np.uint64) == keys_ref).all(), "sort keys differ"
+
+
 def test_mapper_empty_and_culled():
     cfg = RasterConfig()
     o2p, ranges = gs.map_to_tiles(torch.zeros((0, 7), device=DEV), torch.zeros((0, 1), device=DEV), (40, 30), cfg)
@@ -221,7 +289,8 @@ def test_sh_forward_over_a_row_list():
 
 def test_hip_lib_cumsum_and_sort():
     rng = np.random.default_rng(0)
-    for n in (1, 2, 1023, 1024, 1025, 100000, 1 << 20):
+    # (1 << 20) + 1: 1025 block sums, the first second round (and carry) of the scan over them
+    for n in (1, 2, 1023, 1024, 1025, 100000, 1 << 20, (1 << 20) + 1):
         x = rng.integers(0, 50, n).astype(np.int32)
         out, total = gs.hip_lib.full_cumsum(dev(x))
         ref = np.concatenate([[0], np.cumsum(x.astype(np.int64))])
