@@ -566,6 +566,36 @@ int gs_optim_step_rows(int32_t laprop, int32_t vector_group, int64_t rows, int32
                        int32_t bias_correction, float* lr_step, const float* row_scale, float* param,
                        const float* mask_lr, const float* point_lr, void* stream);
 
+/* ------------------------------------------------------------------- row lists of several views (rows.hip)
+ * A step over a batch of views: each view's backward lists its visible rows ascending and distinct, so the index list
+ * of a gradient summed over B backward passes is a concatenation of at most B strictly ascending RUNS.  The three entry
+ * points below find the runs, sum the value rows of the runs for the rows of a step, and form the union of the views'
+ * row lists, without a sort.  An empty call (count == 0, rows == 0, n == 0) writes nothing and returns 0. */
+#define GS_ROWS_MAX_RUNS 16
+
+/* rows (count int64) seen as the concatenation of its maximal STRICTLY ascending runs: a run starts at 0 and at
+ * every i with rows[i] <= rows[i-1].  *run_count (device) = the true number of runs, also when it exceeds max_runs;
+ * run_starts (device, max_runs + 1) = the starts of the first min(runs, max_runs) runs, ascending, followed by the
+ * start of the next run or `count` (and `count` in every entry behind that).  1 <= max_runs <= GS_ROWS_MAX_RUNS. */
+int gs_rows_find_runs(int64_t count, const int64_t* rows, int32_t max_runs, int64_t* run_starts,
+                      int32_t* run_count, void* stream);
+
+/* out (rows, dims) = for each indexes[i] the sum, IN RUN ORDER, of the value rows that list it (one binary search
+ * per run; a strictly ascending run lists a row at most once); zeros where no run lists it.  runs is the host's
+ * copy of *run_count, 0 <= runs <= GS_ROWS_MAX_RUNS; run_starts holds runs + 1 entries (entries outside
+ * [0, grad_count] are clamped into it); grad_values (grad_count, dims) contiguous.  The result is a deterministic
+ * function of the inputs: the same bits on every call. */
+int gs_rows_sum_runs(int64_t rows, const int64_t* indexes, int32_t runs, const int64_t* run_starts,
+                     int64_t grad_count, const int64_t* grad_indexes, int32_t dims, const float* grad_values,
+                     float* out, void* stream);
+
+/* ascending distinct union of rows (count int64, any order, repeats allowed) inside [0, n): a bitmap of n bits in
+ * scratch (mark, word-popcount scan, emit).  Entries outside [0, n) are skipped.  union_rows has capacity
+ * min(count, n); *union_count on the device.  scratch: 16-byte aligned.  n < 2^31. */
+int64_t gs_rows_union_scratch_bytes(int64_t n);
+int gs_rows_union(int64_t n, int64_t count, const int64_t* rows, int64_t* union_rows, int32_t* union_count,
+                  void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
  * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are

@@ -155,6 +155,11 @@ SIGNATURES = {
     "gs_optim_grad_rows": (ctypes.c_int, [_I64, _P, _I64, _P, _P, _P]),
     "gs_optim_step_rows": (ctypes.c_int, [_I32, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, c_float, c_float,
                                            c_float, c_float, _I32, _P, _P, _P, _P, _P, _P]),
+    # row lists of several views: ascending runs, their sum for the rows of a step, the union of the lists
+    "gs_rows_find_runs": (ctypes.c_int, [_I64, _P, _I32, _P, _P, _P]),
+    "gs_rows_sum_runs": (ctypes.c_int, [_I64, _P, _I32, _P, _I64, _P, _I32, _P, _P, _P]),
+    "gs_rows_union_scratch_bytes": (_I64, [_I64]),
+    "gs_rows_union": (ctypes.c_int, [_I64, _I64, _P, _P, _P, _P, _I64, _P]),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),

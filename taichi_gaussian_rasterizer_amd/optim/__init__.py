@@ -8,9 +8,11 @@ kernel (gs_optim_step).  `ParameterClass` (optim/parameter_class.py: parameters 
 follows pruning and densification) is provided on a plain tensor table instead of tensordict.
 """
 from .autograd import restore_grad
-from .fractional import FractionalAdam, FractionalLaProp, SparseAdam, SparseLaProp
+from .fractional import FractionalAdam, FractionalLaProp, SparseAdam, SparseLaProp, gather_sparse_grad
 from .parameter_class import ParameterClass, TensorTable
+from .rows import union_rows, visible_union
 from .visibility_aware import VisibilityAwareAdam, VisibilityAwareLaProp
 
 __all__ = ['FractionalAdam', 'FractionalLaProp', 'SparseAdam', 'SparseLaProp', 'VisibilityAwareAdam',
-           'VisibilityAwareLaProp', 'ParameterClass', 'TensorTable', 'restore_grad']
+           'VisibilityAwareLaProp', 'ParameterClass', 'TensorTable', 'restore_grad', 'gather_sparse_grad', 'union_rows',
+           'visible_union']

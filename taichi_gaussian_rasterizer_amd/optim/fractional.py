@@ -17,18 +17,29 @@ it: the step then reads the compact (V, D) values in place (gs_optim_step_rows);
 not list takes a zero gradient, as it would from the dense tensor.  A gradient that is one backward of one frame is
 recognised by the address of its index list (fused.is_frame_sparse_grad) and trusted to be ascending: `indexes` is
 matched against it by one binary-search launch, no host copy, no sort.  Any other sparse gradient -- summed over several
-backward passes, built by hand, zero_grad(set_to_none=False) -- goes through `coalesce()` first: correct, but slower.
+backward passes, built by hand, zero_grad(set_to_none=False) -- is seen as a concatenation of strictly ascending runs
+(gs_rows_find_runs; the sum of B frame gradients has at most B, however autograd laid it out).  With at most
+GS_ROWS_MAX_RUNS of them the gradient rows of the step's `indexes` are summed in run order (gs_rows_sum_runs: one
+binary search per run, no sort) and the step reads those; this costs one 4-byte host read per step, the run counts of all
+groups together.  With more runs, or with MERGE_RUNS = False, the gradient goes through `coalesce()` first: correct, but
+slower.
 """
 from __future__ import annotations
 
+from functools import cached_property
 from typing import Optional
 
 import torch
 
 from .. import _native as nv
+from . import rows as row_lists
 
 ADAM, LAPROP = 0, 1
 _GROUP_TYPES = ("scalar", "vector", "local_vector")
+
+# False: every sparse gradient that is neither a frame's own nor coalesced goes through coalesce(), and union_rows
+# through torch.unique -- the path before the run kernels existed, for A/B runs
+MERGE_RUNS = True
 
 
 def saturate(x: torch.Tensor) -> torch.Tensor:
@@ -49,11 +60,15 @@ class _Rows:
             raise ValueError(f"unknown group type {self.kind}")
         self.num_points = tensor.shape[0]
         self.param = tensor.view(self.num_points, -1)
-        grad = tensor.grad
+
+    @cached_property
+    def grad(self):
+        """None, the (N, D) view of a dense gradient, or the _SparseRows of a sparse one -- formed on first use, since
+        forming the latter may launch (find_runs) or sort (coalesce)"""
+        grad = self.tensor.grad
         if grad is not None and grad.is_sparse:
-            self.grad = _SparseRows(grad, self.param.shape[1])
-        else:
-            self.grad = None if grad is None else grad.view(self.num_points, -1)
+            return _SparseRows(grad, self.param.shape[1])
+        return None if grad is None else grad.view(self.num_points, -1)
 
     @property
     def per_row_moment(self) -> bool:
@@ -81,18 +96,59 @@ class _Rows:
 
 
 class _SparseRows:
-    """A sparse row gradient seen as an ascending list of distinct rows (R) and their values (R, D)."""
+    """A sparse row gradient seen as an ascending list of distinct rows (R) and their values (R, D) -- or, while
+    `run_starts` is set, as up to GS_ROWS_MAX_RUNS such lists one behind the other (a sum over several backward
+    passes), which `for_step` turns into the former for the rows of one step."""
 
     def __init__(self, grad: torch.Tensor, width: int):
         from ..fused import is_frame_sparse_grad
         if grad.sparse_dim() != 1:
             raise ValueError(f"a sparse gradient must be sparse over rows only, got sparse_dim {grad.sparse_dim()}")
-        if not (grad.is_coalesced() or is_frame_sparse_grad(grad)):
-            grad = grad.coalesce()  # the slow path: sorts, and sums repeated rows
+        self.width, self.runs, self.run_starts, self.run_count = width, 0, None, None
+        if grad.is_coalesced() or is_frame_sparse_grad(grad):
+            self._adopt(grad)
+        elif MERGE_RUNS and grad._nnz() > 0:
+            self._adopt(grad)
+            self.indexes = self.indexes.contiguous()
+            self.run_starts, self.run_count = row_lists.find_runs(self.indexes)  # read on the host by settle_runs
+            self._grad = grad
+        else:
+            self._adopt(grad.coalesce())  # the slow path: sorts, and sums repeated rows
+
+    def _adopt(self, grad: torch.Tensor) -> None:
         self.indexes = grad._indices()[0]
-        self.values = grad._values().reshape(self.indexes.shape[0], width)
+        self.values = grad._values().reshape(self.indexes.shape[0], self.width)
         if not self.values.is_contiguous():
             self.values = self.values.contiguous()
+
+    @staticmethod
+    def settle_runs(grads) -> None:
+        """the one host read of a step: the run counts of every gradient that waits for one.  A gradient of more than
+        GS_ROWS_MAX_RUNS runs goes through coalesce() after all."""
+        waiting = [g for g in grads if isinstance(g, _SparseRows) and g.run_count is not None]
+        if not waiting:
+            return
+        counts = (waiting[0].run_count if len(waiting) == 1 else torch.cat([g.run_count for g in waiting])).tolist()
+        for g, runs in zip(waiting, counts):
+            g.run_count = None
+            if runs <= row_lists.MAX_RUNS:
+                g.runs = int(runs)
+            else:
+                g.run_starts = None
+                g._adopt(g._grad.coalesce())
+            g._grad = None
+
+    def for_step(self, indexes: torch.Tensor) -> "_SparseRows":
+        """the gradient as one list: itself, or -- made of runs -- the (len(indexes), D) rows of `indexes`, each the
+        sum of its rows in the runs in run order, listed under `indexes` itself (rows_of: row i)"""
+        assert self.run_count is None, "settle_runs first"
+        if self.run_starts is None:
+            return self
+        summed = _SparseRows.__new__(_SparseRows)
+        summed.width, summed.runs, summed.run_starts, summed.run_count = self.width, 0, None, None
+        summed.indexes = indexes
+        summed.values = row_lists.sum_runs(indexes, self.runs, self.run_starts, self.indexes, self.values)
+        return summed
 
     def rows_of(self, indexes: torch.Tensor, cache: Optional[dict]):
         """int32 (len(indexes)): the row of `values` that holds the gradient of indexes[i], -1 for none; None when
@@ -119,6 +175,26 @@ class _SparseRows:
             return self.values.new_zeros((count, self.values.shape[1]))
         at = grad_rows.to(torch.int64)
         return self.values[at.clamp_min(0)] * (at >= 0).unsqueeze(1)
+
+
+@torch.no_grad()
+def gather_sparse_grad(grad: torch.Tensor, indexes: torch.Tensor) -> torch.Tensor:
+    """(len(indexes), D) float32: the rows `indexes` of a sparse row gradient (N, ...), D = the elements of a row, zeros
+    where the gradient lists none; repeated rows of the gradient summed.  The three paths of the optimizer step: a frame's
+    own or a coalesced gradient is read in place, a sum over up to GS_ROWS_MAX_RUNS backward passes run by run
+    (in run order), anything else through coalesce()."""
+    if not grad.is_sparse:
+        raise TypeError("gather_sparse_grad takes a torch.sparse_coo gradient over rows")
+    width = 1
+    for extent in grad.shape[1:]:
+        width *= int(extent)
+    indexes = indexes.contiguous()
+    nv.require_device(indexes, dtype=torch.int64, what="gather_sparse_grad indexes")
+    nv.require_device(grad._values(), what="gather_sparse_grad values")
+    rows = _SparseRows(grad, width)
+    _SparseRows.settle_runs([rows])
+    rows = rows.for_step(indexes)
+    return rows.gather(rows.rows_of(indexes, None), indexes.shape[0])
 
 
 def _launch(rows: _Rows, algorithm: int, indexes, weight, total_weight, grad, row_scale, in_place: bool,
@@ -179,6 +255,7 @@ def update_rows(rows: _Rows, algorithm: int, indexes: torch.Tensor, weight: torc
     extra = {}
     if sparse:
         indexes = indexes.contiguous()
+        grad = grad.for_step(indexes)
         extra = dict(grad_rows=grad.rows_of(indexes, cache), compact=True)
     if rows.kind == "local_vector" and sparse:
         assert basis is not None, "basis is required for local_vector optimizer"
@@ -252,6 +329,7 @@ class FractionalOpt(torch.optim.Optimizer):
         if not counted:
             total_weight[indexes] += weight
         cache = {}
+        _SparseRows.settle_runs([view.grad for view in views])
         for view in views:
             if view.grad is not None:
                 update_rows(view, self.algorithm, indexes, weight, total_weight, basis, row_scale, cache)
