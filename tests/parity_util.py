@@ -26,6 +26,18 @@ FLIP_MARGIN = 5e-6
 # projected mean and axes (~1e-4 px at 2048 px, relative 6e-8 of coordinates up to 2e3), which moves alpha by
 # |d ln alpha / dx| * 1e-4 = (r / sigma^2) * 1e-4 <= ~1e-3 relative for the sub-pixel sigmas of the test scenes
 E2E_FLIP_MARGIN = 2e-3
+# ... which leaves out the AXIS.  The major axis is (c00 - l2, c01) normalised (generic.py:217-230; project_math.h has
+# the same form): for a splat whose major axis lies along y both components are differences of nearly equal numbers, and
+# ANY f32 evaluation gets the direction wrong by ~1e-2 rad (measured: the f32 oracle's axis is up to 1.5e-2 rad off the
+# f64 oracle's on the scene below, at an eigenvalue gap of 0.08, where the existing tests exclude nothing).  With
+# (sigma1 - sigma2) / sigma = 0.08 that moves alpha at the splat's rim by several 1e-3 relative.  Measured with the
+# oracle alone on the settings sweep's frames (config_cases.FRAMES; test_config_sweep_cpu.py repeats the measurement):
+# the f32 oracle pipeline against the f64 one has one pixel out of the end-to-end tolerance, in frame_b, with margin
+# 2.43e-3 and error 5.51e-3 -- on the MI355X the same pixel, with the same error, is the HIP pipeline's only outlier
+# against the f32 oracle (one flip of that splat either way).  Bar: 1e-2 (4x the measured margin, the headroom of the
+# bars above), for the splats of that frame whose axis the two oracles place more than 1e-3 rad apart and for nothing
+# else (config_cases.frame_flip_proof): every other splat and every other frame keeps E2E_FLIP_MARGIN.
+E2E_AXIS_FLIP_MARGIN = 1e-2
 # the antialiased pdf (taichi_lib/generic.py:341-357) is a product of two DIFFERENCES of sigmoids, S(a) - S(b): each
 # sigmoid carries ~6e-8 of absolute rounding while the difference itself is ~1e-2 ... 1e-3 where alpha sits at the
 # threshold in a splat's tail, and the HIP forward evaluates the difference in the cancellation-free form

@@ -1,10 +1,13 @@
 """float64 projection, SH and rasterizer on the GPU (csrc/*_f64.hip): the reference's own f64 golden bar, gradcheck of
 each operator, parity with the f64 oracle, the visibility identity and bit reproducibility."""
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
 from torch.autograd import gradcheck
 
+import config_cases as cc
 import parity_util as pu
 import taichi_gaussian_rasterizer_amd as gs
 from golden_util import projection_cases, sh_cases
@@ -88,6 +91,57 @@ def test_raster_gradcheck_reference_scene(seed, antialias):
     assert gradcheck(_raster_fn(o2p, ranges, size, cfg), (*_split(g2d), colours), **GRADCHECK)
 
 
+OTHER_SETTINGS = dict(tile_size=8, pixel_stride=(1, 1), alpha_threshold=1e-3, clamp_max_alpha=0.7, saturate_threshold=1.0)
+
+
+def _reference_scene_at_other_settings(alpha_range):
+    """test_raster_gradcheck_reference_scene's scene (seed 0) with the threshold, the clamp and the saturation level
+    away from their defaults; also returns how far the clamp moves the image (against 0.99)"""
+    torch.manual_seed(0)
+    n = torch.randint(1, 50, (1,)).item()
+    channels = torch.randint(1, 4, (1,)).item()
+    size = (8, 8)
+    g = scenes.random_2d_gaussians(n, size, num_channels=channels, scale_factor=1.0, alpha_range=alpha_range)
+    g2d = project_gaussians2d(g).to(DEV, F64)
+    colours = g.feature.to(DEV, F64).requires_grad_(True)
+    cfg = RasterConfig(**OTHER_SETTINGS)
+    o2p = torch.arange(n, dtype=torch.int32, device=DEV)
+    ranges = torch.tensor([[0, n]], dtype=torch.int32, device=DEV)
+    with torch.no_grad():
+        free = gs.rasterize_with_tiles(g2d, colours, o2p, ranges, size, dataclasses.replace(cfg, clamp_max_alpha=0.99))
+        held = gs.rasterize_with_tiles(g2d, colours, o2p, ranges, size, cfg)
+        low = gs.rasterize_with_tiles(g2d, colours, o2p, ranges, size,
+                                      dataclasses.replace(cfg, alpha_threshold=1.0 / 255.0))
+    assert float((low.image - held.image).abs().max()) > 1e-4, "the threshold must decide some pixel"
+    return g2d, colours, o2p, ranges, size, cfg, float((free.image - held.image).abs().max())
+
+
+def test_raster_gradcheck_reference_scene_at_other_settings():
+    """every input, opacities in (0.2, 0.65): below the clamp of 0.7 the backward is the derivative of the forward.
+    At saturate_threshold = 1 the backward never stops a pixel, so the analytic gradient is that of the whole blend.
+    The clamp never holds here (asserted), so this gradcheck constrains alpha_threshold and saturate_threshold only and
+    would pass with the clamp fixed at 0.99; the clamp is covered by the next test and by
+    test_raster_matches_f64_oracle[seed6] and [seed8]."""
+    g2d, colours, o2p, ranges, size, cfg, clamp_effect = _reference_scene_at_other_settings((0.2, 0.65))
+    assert clamp_effect == 0.0
+    assert gradcheck(_raster_fn(o2p, ranges, size, cfg), (*_split(g2d), colours), **GRADCHECK)
+
+
+def test_raster_gradcheck_colours_where_the_clamp_holds():
+    """opacities in (0.2, 0.8) as in the reference's scene: one splat is held at 0.7 on the pixels at its centre.  There
+    the reference's backward hands the splat's own geometry the gradient of the UNCLAMPED alpha (backward.py:166-169
+    tests and differentiates the raw alpha, then clamps; the oracle and the kernels follow it), so the gradient is not
+    the derivative of the forward for that splat's row and a gradcheck over the geometry cannot pass: the float64 oracle
+    itself is 1.5e-2 off its own central differences in that one row, 3e-10 in every other and in every row at 0.99.
+    Those rows are held to the oracle by test_raster_matches_f64_oracle[seed6] and [seed8]; what is exact through the
+    clamp is the gradient of the colours, and it is checked here."""
+    g2d, colours, o2p, ranges, size, cfg, clamp_effect = _reference_scene_at_other_settings((0.2, 0.8))
+    assert clamp_effect > 1e-3, "the clamp must hold some pixel"
+    mean, axis, sigma, alpha = (t.detach() for t in _split(g2d))
+    fn = _raster_fn(o2p, ranges, size, cfg)
+    assert gradcheck(lambda c: fn(mean, axis, sigma, alpha, c), (colours,), **GRADCHECK)
+
+
 @pytest.mark.parametrize("seed,tile,size,n", [(0, 8, (37, 21), 14), (1, 16, (40, 23), 14), (2, 32, (45, 21), 12)])
 def test_raster_gradcheck_across_tiles(seed, tile, size, n):
     """lists from the float32 mapper, held fixed; image sizes that are not tile multiples; splats in several lists so
@@ -166,6 +220,30 @@ def test_projection_gradcheck_clamp_and_cull():
     assert gradcheck(fn, [t.detach().requires_grad_(True) for t in leaves], **GRADCHECK)
 
 
+def test_projection_gradcheck_without_margin_and_with_a_wide_blur():
+    """clamp_margin = 0: every mean outside the image takes the clamp's zero-gradient branch (rows 1 and 3 here);
+    blur_cov = 1 dominates the covariance of the small splats"""
+    inputs, size, depth_range = clamp_and_cull_scene()
+    kw = dict(blur_cov=1.0, clamp_margin=0.0)
+    ref_points, _, ref_idx = orc.project(*(t.numpy() for t in inputs), size, depth_range, **kw)
+    u, v = ref_points[:, 0], ref_points[:, 1]
+    outside = (u < 0) | (u > size[0] - 1) | (v < 0) | (v > size[1] - 1)
+    assert int(outside.sum()) >= 2 and int((~outside).sum()) >= 3
+    away = 1e-3 * size[0]
+    assert min(np.abs(u).min(), np.abs(u - (size[0] - 1)).min(), np.abs(v).min(), np.abs(v - (size[1] - 1)).min()) >= away
+    leaves = [t.to(DEV).requires_grad_(True) for t in inputs]
+    points, depth, idx = hip_proj.apply(*leaves, size, depth_range, **kw)
+    assert (pu.to_np(idx) == ref_idx).all()
+    assert np.allclose(pu.to_np(points), ref_points, rtol=1e-9, atol=1e-12)
+    default_points, _, _ = hip_proj.apply(*leaves, size, depth_range)
+    assert float((points[:, 4:6] - default_points[:, 4:6]).abs().min()) > 1e-3, "every sigma must move"
+
+    def fn(*t):
+        points, depth, _ = hip_proj.apply(*t, size, depth_range, **kw)
+        return points, depth
+    assert gradcheck(fn, [t.detach().requires_grad_(True) for t in leaves], **GRADCHECK)
+
+
 @pytest.mark.parametrize("degree", [0, 1, 2, 3])
 def test_sh_gradcheck_repeated_indexes(degree):
     torch.manual_seed(degree)
@@ -191,13 +269,22 @@ PARITY = [
     dict(seed=3, n=1500, size=(130, 100), cfg=dict(tile_size=32, compute_visibility=True,
                                                    compute_point_heuristic=True)),
     dict(seed=4, n=1500, size=(120, 80), cfg=dict(tile_size=16, use_alpha_blending=False, saturate_threshold=0.5)),
+    # thresholds, clamps and levels away from the defaults (config_cases.CONFIGS), opacities up to 1
+    dict(seed=5, n=1200, size=(130, 75), alpha_range=(0.05, 1.0), cfg=dict(tile_size=16, **cc.CONFIGS["thr_small"])),
+    dict(seed=6, n=1200, size=(101, 67), alpha_range=(0.05, 1.0), cfg=dict(tile_size=8, **cc.CONFIGS["clamp_half"])),
+    dict(seed=7, n=1200, size=(130, 75), alpha_range=(0.05, 1.0), scale_factor=0.8,
+         cfg=dict(tile_size=32, **cc.CONFIGS["sat_half"])),
+    dict(seed=8, n=1200, size=(101, 67), alpha_range=(0.05, 1.0), scale_factor=0.8,
+         cfg=dict(tile_size=16, compute_point_heuristic=True, **cc.CONFIGS["mixed"])),
+    dict(seed=9, n=1200, size=(130, 75), alpha_range=(0.05, 1.0), cfg=dict(tile_size=16, **cc.CONFIGS["aa_mixed"])),
 ]
 
 
 @pytest.mark.parametrize("case", PARITY, ids=[f"seed{c['seed']}" for c in PARITY])
 def test_raster_matches_f64_oracle(case):
     """the bars the oracle meets against the dense f64 renderer (tests/test_oracle_raster.py:36-45)"""
-    g2d, depth, feat = _scene(case["seed"], case["n"], case["size"], channels=case.get("channels", 3))
+    g2d, depth, feat = _scene(case["seed"], case["n"], case["size"], channels=case.get("channels", 3),
+                              scale_factor=case.get("scale_factor", 0.5), alpha_range=case.get("alpha_range", (0.2, 0.8)))
     size = case["size"]
     cfg = RasterConfig(**case["cfg"])
     o2p, ranges = gs.map_to_tiles(g2d.float(), depth, size, cfg)

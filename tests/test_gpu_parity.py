@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import config_cases as cc
 import parity_util as pu
 from golden_util import load_cases, projection_cases, sh_cases
 from oracle import oracle as orc
@@ -35,8 +36,24 @@ MAPPER_CASES = [(0, 500, (320, 200), 16, False), (1, 2000, (257, 131), 16, False
 
 @pytest.mark.parametrize("seed,n,size,tile,depth16", MAPPER_CASES)
 def test_mapper_bit_exact(seed, n, size, tile, depth16):
+    _mapper_bit_exact(seed, n, size, RasterConfig(tile_size=tile), depth16)
+
+
+@pytest.mark.parametrize("depth16", [False, True])
+@pytest.mark.parametrize("tile", [8, 16, 32])
+@pytest.mark.parametrize("thr", [1e-4, 1.0 / 255.0, 0.05, 0.3])
+def test_mapper_bit_exact_at_other_thresholds(thr, tile, depth16):
+    """the tile query's extent is sqrt(2 ln(alpha / thr)) through the deterministic ln and sqrt (map_query.h): from
+    r ~ 4.3 sigma at 1e-4 to opacities below the threshold (no tile at all) at 0.3"""
+    cfg = RasterConfig(tile_size=tile, alpha_threshold=thr)
+    k = _mapper_bit_exact(1, 2000, (257, 131), cfg, depth16)
+    k_default = orc.map_to_tiles(*pu.make_2d_scene(1, 2000, (257, 131), scale_factor=0.7, alpha_range=(0.001, 1.0))[:2],
+                                 (257, 131), orc.OracleConfig.of(RasterConfig(tile_size=tile)))[0].shape[0]
+    assert (k == k_default) == (thr == 1.0 / 255.0), "the threshold must change the overlap count"
+
+
+def _mapper_bit_exact(seed, n, size, cfg, depth16):
     g2d, depth, _ = pu.make_2d_scene(seed, n, size, scale_factor=0.7, alpha_range=(0.001, 1.0))
-    cfg = RasterConfig(tile_size=tile)
     o2p_ref, ranges_ref, keys_ref = orc.map_to_tiles(g2d, depth, size, orc.OracleConfig.of(cfg), depth16, return_keys=True)
     for fn in (gs.map_to_tiles, map_to_tiles_reference_stages):
         o2p, ranges, keys = fn(dev(g2d), dev(depth), size, cfg, use_depth16=depth16, return_keys=True)
@@ -46,17 +63,25 @@ def test_mapper_bit_exact(seed, n, size, tile, depth16):
         assert (pu.to_np(ranges) == ranges_ref).all(), f"{fn.__name__}: tile ranges differ"
         assert (pu.to_np(o2p) == o2p_ref).all(), f"{fn.__name__}: overlap order differs"
         assert (pu.to_np(keys).view(np.uint64) == keys_ref).all(), f"{fn.__name__}: sort keys differ"
+    return int(o2p_ref.shape[0])
 
 
 @pytest.mark.parametrize("n", [600, 1500, 4000, 7000, 9000])
 def test_mapper_crowded_tile(n):
     """one tile holding more splats than the wave rank sort covers (512): workgroup merge sort in LDS up to 8192,
     in-place global-memory bitonic network beyond"""
+    _mapper_crowded_tile(n, RasterConfig())
+
+
+def test_mapper_crowded_tile_at_a_low_threshold():
+    _mapper_crowded_tile(1500, RasterConfig(alpha_threshold=1e-4))
+
+
+def _mapper_crowded_tile(n, cfg):
     torch.manual_seed(0)
     g2d = torch.cat([torch.rand(n, 2) * 14 + 1, torch.tensor([[1.0, 0.0]]).expand(n, 2), torch.rand(n, 2) + 0.5,
                      torch.rand(n, 1) * 0.5 + 0.3], 1).float()
     depth = torch.rand(n, 1)
-    cfg = RasterConfig()
     o2p_ref, ranges_ref = orc.map_to_tiles(g2d, depth, (16, 16), orc.OracleConfig.of(cfg))
     o2p, ranges = gs.map_to_tiles(dev(g2d), dev(depth), (16, 16), cfg)
     assert (pu.to_np(ranges) == ranges_ref).all() and (pu.to_np(o2p) == o2p_ref).all()
@@ -371,12 +396,29 @@ def test_raster_extreme_opacities(heur):
     """the lean kernels stage -log2(opacity) and let v_exp_f32 return alpha: opacities at the threshold, at and beyond
     the clamp (0.99) and above 1 (a caller's own 2D splats may carry any value) against the oracle's
     opacity * exp(...) -- forward, backward and (heur) the densification statistics of the MODE 1 kernels"""
-    size, n, F = (96, 64), 600, 3
-    g2d, depth, feat = pu.make_2d_scene(21, n, size, channels=F, scale_factor=0.6)
     cfg = RasterConfig(compute_point_heuristic=heur)
     thr = cfg.alpha_threshold
-    vals = np.array([thr * (1 - 1e-3), thr * (1 + 1e-3), thr * 1.5, 0.05, 0.5, 0.98, 0.99, 0.995, 1.0, 1.5, 4.0],
-                    np.float32)
+    _raster_extreme_opacities(cfg, [thr * (1 - 1e-3), thr * (1 + 1e-3), thr * 1.5, 0.05, 0.5, 0.98, 0.99, 0.995, 1.0,
+                                    1.5, 4.0])
+
+
+@pytest.mark.parametrize("heur", [False, True], ids=["lean", "heur"])
+@pytest.mark.parametrize("cid", ["thr_small", "clamp_half", "mixed"])
+def test_raster_extreme_opacities_at_other_settings(cid, heur):
+    """the ladder rebuilt around the setting's threshold and clamp: just under and over the threshold, at and over the
+    clamp, and above 1"""
+    cfg = cc.raster_config(cid, 16, compute_point_heuristic=heur)
+    thr, cmax = cfg.alpha_threshold, cfg.clamp_max_alpha
+    _raster_extreme_opacities(cfg, [thr * (1 - 1e-3), thr * (1 + 1e-3), thr * 1.5, 0.05, 0.5 * cmax, cmax * (1 - 1e-3),
+                                    cmax, cmax * (1 + 1e-3), 1.0, 1.5, 4.0], scale_bar=True)
+
+
+def _raster_extreme_opacities(cfg, vals, scale_bar=False):
+    """vals[0] is below the threshold: the rows that carry it must get an exactly zero gradient"""
+    heur = cfg.compute_point_heuristic
+    size, n, F = (96, 64), 600, 3
+    g2d, depth, feat = pu.make_2d_scene(21, n, size, channels=F, scale_factor=0.6)
+    vals = np.array(vals, np.float32)
     g2d = pu.to_np(g2d).copy()
     g2d[:, 6] = vals[np.arange(n) % len(vals)]
     ocfg = orc.OracleConfig.of(cfg)
@@ -384,7 +426,8 @@ def test_raster_extreme_opacities(heur):
     image_ref, alpha_ref, _ = orc.rasterize_with_tiles(g2d, feat, o2p, ranges, size, ocfg)
     g_t, f_t = dev(g2d).requires_grad_(True), dev(feat).requires_grad_(True)
     out = gs.rasterize_with_tiles(g_t, f_t, dev(o2p), dev(ranges.reshape(-1, 2)), size, cfg)
-    proof = pu.flip_proof(g2d, feat, o2p, ranges, size, ocfg)
+    proof = pu.flip_proof(g2d, feat, o2p, ranges, size, ocfg,
+                          bar=cc.raster_bar(cfg, g2d) if scale_bar else pu.FLIP_MARGIN)
     pu.assert_pixels_close(out.image, image_ref, "image", flips=proof)
     pu.assert_pixels_close(out.image_weight, alpha_ref, "alpha", flips=proof.weight())
     gi = torch.rand(size[1], size[0], F, generator=torch.Generator().manual_seed(22))
@@ -658,8 +701,19 @@ def test_render_gaussians_stagewise(seed, n, size, deg, depth_mode, frame_path):
     """render_gaussians == the composition of the HIP operators, and every stage of that composition
     matches the oracle when the oracle is fed the HIP stage's own inputs (tight tolerances: no
     compounding of f32 rounding through the pipeline)."""
+    _render_gaussians_stagewise(seed, n, size, deg, depth_mode, RasterConfig())
+
+
+@pytest.mark.parametrize("depth_mode", [False, True])
+@pytest.mark.parametrize("fid", list(cc.FRAMES))
+def test_render_gaussians_stagewise_at_other_settings(fid, depth_mode, frame_path):
+    """the same at tile sizes 8 and 32 and with every threshold, clamp, margin and blur away from its default"""
+    s = cc.FRAME_SCENE
+    _render_gaussians_stagewise(s["seed"], s["n"], s["size"], s["sh_degree"], depth_mode, cc.frame_config(fid))
+
+
+def _render_gaussians_stagewise(seed, n, size, deg, depth_mode, cfg):
     g, camera = scenes.benchmark_scene(n, size, sh_degree=deg, seed=seed)
-    cfg = RasterConfig()
     ocfg = orc.OracleConfig.of(cfg)
     gen = torch.Generator().manual_seed(seed + 7)
     gi = torch.rand(size[1], size[0], 3, generator=gen)
@@ -700,7 +754,7 @@ def test_render_gaussians_stagewise(seed, n, size, deg, depth_mode, frame_path):
     f_np = pu.to_np(feats)
     feats_r = np.concatenate([d_np, d_np ** 2, f_np], 1).astype(np.float32) if depth_mode else f_np
     image_ref, alpha_ref, _ = orc.rasterize_with_tiles(p_np, feats_r, o2p_ref, ranges_ref, size, ocfg)
-    proof = pu.flip_proof(p_np, feats_r, o2p_ref, ranges_ref, size, ocfg)
+    proof = pu.flip_proof(p_np, feats_r, o2p_ref, ranges_ref, size, ocfg, bar=cc.raster_bar(cfg, p_np))
     g_img = np.zeros_like(image_ref)
     if depth_mode:
         pu.assert_pixels_close(r.image, image_ref[..., 2:], "image", flips=proof.channels(slice(2, None)))
@@ -722,7 +776,10 @@ def test_render_gaussians_stagewise(seed, n, size, deg, depth_mode, frame_path):
         hip_img = pu.to_np(r.image)
         g_img[...] = gi.numpy()
     pu.assert_pixels_close(r.image_weight, alpha_ref, "image_weight", flips=proof.weight())
-    gg, gf, _ = orc.rasterize_backward(p_np, feats_r, o2p_ref, ranges_ref, size, hip_img.astype(np.float32), g_img, ocfg)
+    gg, gf, heur = orc.rasterize_backward(p_np, feats_r, o2p_ref, ranges_ref, size, hip_img.astype(np.float32), g_img,
+                                          ocfg)
+    if cfg.compute_point_heuristic:
+        pu.assert_grad_close(r.point_heuristic, heur, "point_heuristic", tol=1e-3)
     gdepth_ref = np.zeros_like(d_np)
     if depth_mode:
         gdepth_ref = gf[:, 0:1] + 2 * d_np * gf[:, 1:2]
@@ -736,8 +793,9 @@ def test_render_gaussians_stagewise(seed, n, size, deg, depth_mode, frame_path):
     up_d = pu.to_np(depths.grad) if depths.grad is not None else np.zeros_like(d_np)
     args64 = [a.double() for a in args]
     truth = orc.project_backward(*args64, size, pu.to_np(idx), pu.to_np(g2d.grad).astype(np.float64),
-                                 up_d.astype(np.float64), blur_cov=cfg.blur_cov)
-    cpu32 = orc.project_backward(*args, size, pu.to_np(idx), pu.to_np(g2d.grad), up_d, blur_cov=cfg.blur_cov)
+                                 up_d.astype(np.float64), blur_cov=cfg.blur_cov, clamp_margin=cfg.clamp_margin)
+    cpu32 = orc.project_backward(*args, size, pu.to_np(idx), pu.to_np(g2d.grad), up_d, blur_cov=cfg.blur_cov,
+                                 clamp_margin=cfg.clamp_margin)
     for name, tr, c32 in zip(("position", "log_scaling", "rotation", "alpha_logit"), truth, cpu32):
         sc = max(float(np.abs(tr).max()), 1e-30)
         cpu_err = float(np.abs(c32 - tr).max()) / sc
@@ -793,11 +851,19 @@ def test_config1_fit_loop_gpu():
 def test_sharded_strips_on_one_gpu(world):
     """the per-rank work of parallel.render_gaussians_sharded, ranks emulated one after another on a
     single GPU: strips tile the full image, summed partial gradients equal the full gradients"""
+    _sharded_strips_on_one_gpu(world, RasterConfig())
+
+
+def test_sharded_strips_on_one_gpu_at_other_settings():
+    """tile size 32 (strips of 32 rows; 176 is no multiple) and frame_b's thresholds, clamp, margin and blur"""
+    _sharded_strips_on_one_gpu(2, cc.frame_config("frame_b"))
+
+
+def _sharded_strips_on_one_gpu(world, cfg):
     from taichi_gaussian_rasterizer_amd import parallel
     size, n = (200, 176), 6000
     g, camera = scenes.benchmark_scene(n, size, sh_degree=3, seed=4)
     cam = camera.to(device=DEV)
-    cfg = RasterConfig()
     gi = dev(torch.rand(size[1], size[0], 3, generator=torch.Generator().manual_seed(9)))
     full = g.to(DEV).requires_grad_(True)
     r = gs.render_gaussians(full, cam, cfg, use_sh=True)
@@ -832,6 +898,18 @@ def test_sharded_strips_on_one_gpu(world):
 
 @pytest.mark.parametrize("interleave", [0, 1])
 def test_rank_local_sh_covers_every_listed_splat(interleave):
+    _rank_local_sh_covers_every_listed_splat(interleave, RasterConfig())
+
+
+@pytest.mark.parametrize("interleave", [0, 1])
+@pytest.mark.parametrize("thr", [1e-4, 0.3], ids=["thr_small", "thr_big"])
+def test_rank_local_sh_covers_every_listed_splat_at_other_thresholds(thr, interleave):
+    """the reach test of gs_sh_fwd_shard has its own copy of the threshold (sh.hip: touch.thr): at 1e-4 the mapper
+    lists splats 1.3x further out than at 1/255, at 0.3 a default extent would still cover them"""
+    _rank_local_sh_covers_every_listed_splat(interleave, RasterConfig(alpha_threshold=thr))
+
+
+def _rank_local_sh_covers_every_listed_splat(interleave, cfg):
     """gs_sh_fwd_shard evaluates colours only for the splats that can reach a rank's rows (0.5 elsewhere): its row test
     must be a superset of the mapper's tile lists.  Long, thin, rotated splats over one-tile-row strips (16 ranks on a
     256-px image, also dealt row by row) are the hard case -- the reference's tile test accepts tiles just outside a
@@ -843,7 +921,6 @@ def test_rank_local_sh_covers_every_listed_splat(interleave):
     g.log_scaling[:, 0] += 1.5 + torch.rand(n, generator=gen)     # 4.5 - 12 x longer along one axis
     g.log_scaling[:, 1:] -= 0.7
     cam = camera.to(device=DEV)
-    cfg = RasterConfig()
     full = gs.render_gaussians(g.to(DEV), cam, cfg, use_sh=True)
     rows = []
     for rank in range(world):
@@ -1080,12 +1157,20 @@ def test_fused_frame_sh_with_camera_gradients(frame_path):
 
 @pytest.mark.parametrize("nb", ["2", "4"])
 def test_fused_frame_splits_heavy_tiles(nb, monkeypatch, frame_path):
+    _fused_frame_splits_heavy_tiles(nb, monkeypatch, RasterConfig())
+
+
+def test_fused_frame_splits_heavy_tiles_at_other_settings(monkeypatch, frame_path):
+    """the 8x8 workgroups of a split tile with a low threshold, a clamp of 0.6 and a saturation level of 0.95"""
+    _fused_frame_splits_heavy_tiles("2", monkeypatch, RasterConfig(**cc.CONFIGS["mixed"]))
+
+
+def _fused_frame_splits_heavy_tiles(nb, monkeypatch, cfg):
     """the mapper marks the fullest tiles of its launch order (counts_out[3]) and the rasterizer gives each of them
     four 8x8 workgroups; with 16x16 / 16x8 wave regions forced on a small, crowded frame a quarter of the tiles take
     that path: pixels must be identical to the unsplit rasterizer, gradients equal up to summation order"""
     from taichi_gaussian_rasterizer_amd.renderer import render_projected
     size, n = (256, 192), 12000
-    cfg = RasterConfig()
     g, camera = scenes.benchmark_scene(n, size, sh_degree=1, seed=21)
     cam = camera.to(device=DEV)
     gi = dev(torch.rand(size[1], size[0], 3, generator=torch.Generator().manual_seed(3)))

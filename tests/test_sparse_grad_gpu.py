@@ -9,6 +9,7 @@ import ctypes
 import pytest
 import torch
 
+import config_cases as cc
 import parity_util as pu
 import taichi_gaussian_rasterizer_amd as gs
 from taichi_gaussian_rasterizer_amd import RasterConfig, _native as nv, scenes
@@ -212,7 +213,19 @@ VALUE_TAIL = dict(position=(3,), log_scaling=(3,), rotation=(4,), alpha_logit=(1
 
 @pytest.mark.parametrize("case", ["sh3", "plain6_depth", "camera"])
 def test_frame_sparse_gradients_match_dense(case, frame_path):
-    g, camera, cfg, kw = _frame_case(case)
+    _frame_sparse_gradients_match_dense(case, *_frame_case(case))
+
+
+@pytest.mark.parametrize("fid", ["frame_a", "frame_b"])
+def test_frame_sparse_gradients_match_dense_at_other_settings(fid, frame_path):
+    """gs_frame_bwd_rows at tile sizes 8 and 32 with every threshold, clamp, margin and blur away from its default, on
+    the settings sweep's scene made half in view, with depth outputs"""
+    s = cc.FRAME_SCENE
+    g, camera = half_in_view(s["n"], s["size"], s["sh_degree"], s["seed"])
+    _frame_sparse_gradients_match_dense(fid, g, camera, cc.frame_config(fid), dict(use_sh=True, render_depth=True))
+
+
+def _frame_sparse_gradients_match_dense(case, g, camera, cfg, kw):
     N = g.position.shape[0]
     C = g.feature.shape[1]
     gi = torch.rand(camera.image_size[1], camera.image_size[0], C, generator=torch.Generator().manual_seed(3)).to(DEV)
