@@ -712,6 +712,60 @@ int gs_photo_loss_bwd_f64(int64_t batch, int64_t height, int64_t width, int64_t 
                           const double* saved_maps, const double* upstream_map, const double* grad_loss,
                           double l1_coeff, double ssim_coeff, double* d_image, void* stream);
 
+/* ------------------------------------------------------- photometric loss, per-pixel weights --
+ * The same loss with a weight w >= 0 per pixel (an object, sky or distractor mask, or a confidence), shared by the
+ * channels: weight (batch, height, width), read through a batch, a row and a pixel stride in ELEMENTS (pixel stride
+ * >= 1, row stride >= width * pixel stride, batch stride >= height * row stride, or 0 = the same weights for every
+ * batch entry), so a column or row view of a larger buffer goes in without a copy.  With S the sum of w over every
+ * pixel and batch entry and S_v the sum over the pixels that enter the SSIM mean (all of them, or with `valid` those
+ * whose window lies inside the image):
+ *   L = sum w |x - y| / (channels * S),  M = sum w ssim_map / (channels * S_v),
+ *   loss = (1 - ssim_weight) * L + ssim_weight * (1 - M).
+ * The map is not changed by the weights: the windows see every pixel of both images.  A term whose weight sum is zero
+ * adds nothing to the loss and exactly zero to the gradient, and its part is NaN.  The weights are expected to be
+ * finite and non-negative; that is not checked.  weight == NULL runs the unweighted loss (S = batch * height * width).
+ *
+ * The argument lists are those of the unweighted calls with the weight and its strides after the target's.
+ * Forward: results (5, device) = [loss, L, M, S, S_v]; scratch: gs_photo_loss_weighted_scratch_bytes.  The weight sums
+ * are added like the other partial sums, in a fixed order and in double: the results repeat bit for bit, all-ones
+ * weights give the bits of the unweighted call, and scaling the weights by a power of two changes nothing.
+ * Backward: normalisers (2, device) = [S, S_v] as the forward wrote them (results + 3): no value comes back to the
+ * host between the two calls.  d_image =
+ *   g * (l1_coeff * dL / dx + ssim_coeff * dM / dx) + sum_q upstream_map(q) * d ssim_map(q) / dx;
+ * upstream_map is not weighted.  No gradient for the weights.  Zero pixels: both calls are no-ops returning 0. */
+int64_t gs_photo_loss_weighted_scratch_bytes(int64_t batch, int64_t height, int64_t width, int64_t channels);
+int gs_photo_loss_weighted_fwd(int64_t batch, int64_t height, int64_t width, int64_t channels, const float* image,
+                               int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                               const float* target, int64_t target_batch_stride, int64_t target_row_stride,
+                               int64_t target_pixel_stride, const float* weight, int64_t weight_batch_stride,
+                               int64_t weight_row_stride, int64_t weight_pixel_stride, int32_t window_size,
+                               double sigma, double data_range, double ssim_weight, int32_t valid, float* ssim_map,
+                               float* saved_maps, void* scratch, int64_t scratch_bytes, float* results, void* stream);
+int gs_photo_loss_weighted_bwd(int64_t batch, int64_t height, int64_t width, int64_t channels, const float* image,
+                               int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                               const float* target, int64_t target_batch_stride, int64_t target_row_stride,
+                               int64_t target_pixel_stride, const float* weight, int64_t weight_batch_stride,
+                               int64_t weight_row_stride, int64_t weight_pixel_stride, const float* normalisers,
+                               int32_t window_size, double sigma, int32_t valid, const float* saved_maps,
+                               const float* upstream_map, const float* grad_loss, double l1_coeff, double ssim_coeff,
+                               float* d_image, void* stream);
+int gs_photo_loss_weighted_fwd_f64(int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                   const double* image, int64_t image_batch_stride, int64_t image_row_stride,
+                                   int64_t image_pixel_stride, const double* target, int64_t target_batch_stride,
+                                   int64_t target_row_stride, int64_t target_pixel_stride, const double* weight,
+                                   int64_t weight_batch_stride, int64_t weight_row_stride, int64_t weight_pixel_stride,
+                                   int32_t window_size, double sigma, double data_range, double ssim_weight,
+                                   int32_t valid, double* ssim_map, double* saved_maps, void* scratch,
+                                   int64_t scratch_bytes, double* results, void* stream);
+int gs_photo_loss_weighted_bwd_f64(int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                   const double* image, int64_t image_batch_stride, int64_t image_row_stride,
+                                   int64_t image_pixel_stride, const double* target, int64_t target_batch_stride,
+                                   int64_t target_row_stride, int64_t target_pixel_stride, const double* weight,
+                                   int64_t weight_batch_stride, int64_t weight_row_stride, int64_t weight_pixel_stride,
+                                   const double* normalisers, int32_t window_size, double sigma, int32_t valid,
+                                   const double* saved_maps, const double* upstream_map, const double* grad_loss,
+                                   double l1_coeff, double ssim_coeff, double* d_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,19 @@ SIGNATURES = {
                                               _F64, _F64, _F64, _I32, _P, _P, _P, _I64, _P, _P]),
     "gs_photo_loss_bwd_f64": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32,
                                               _F64, _I32, _P, _P, _P, _F64, _F64, _P, _P]),
+    "gs_photo_loss_weighted_scratch_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "gs_photo_loss_weighted_fwd": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64,
+                                                   _P, _I64, _I64, _I64, _I32, _F64, _F64, _F64, _I32, _P, _P, _P, _I64,
+                                                   _P, _P]),
+    "gs_photo_loss_weighted_bwd": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64,
+                                                   _P, _I64, _I64, _I64, _P, _I32, _F64, _I32, _P, _P, _P, _F64, _F64,
+                                                   _P, _P]),
+    "gs_photo_loss_weighted_fwd_f64": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64,
+                                                       _I64, _P, _I64, _I64, _I64, _I32, _F64, _F64, _F64, _I32, _P, _P,
+                                                       _P, _I64, _P, _P]),
+    "gs_photo_loss_weighted_bwd_f64": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64,
+                                                       _I64, _P, _I64, _I64, _I64, _P, _I32, _F64, _I32, _P, _P, _P,
+                                                       _F64, _F64, _P, _P]),
 }
 
 _lib = None

@@ -1,7 +1,9 @@
 """Photometric loss (1 - w) * L1 + w * (1 - SSIM): the fused HIP kernels against the same loss composed from torch ops
 (grouped conv2d on channel-first copies, as a trainer without this package writes it).
 
-Phases: fused forward (no_grad), fused forward+backward, torch forward+backward, l1 only (fused, ssim_weight = 0).
+Phases: fused forward (no_grad), fused forward+backward, torch forward+backward, l1 only (fused, ssim_weight = 0),
+fused masked forward+backward (mask= with U(0, 1) weights), map + torch masked forward+backward (the same numbers
+without mask=: the SSIM map weighted by torch ops and a torch L1).
 For the fused phases the compulsory traffic, 44 bytes per pixel-channel forward+backward (8 forward only), over the
 time is printed as a share of the 6.29 TB/s copy rate.  --json PATH: additionally time fused and torch
 forward+backward call by call, alternating, twice each, and write the medians and their spread."""
@@ -13,7 +15,7 @@ import statistics
 import torch
 import torch.nn.functional as F
 
-from ..losses import photometric_loss
+from ..losses import photometric_loss, ssim
 from .util import Phases, make_parser
 
 parse_args = make_parser(("profile", "image_size", "device", "seed", "iters", "num_channels", "ssim_weight", "json",
@@ -42,6 +44,20 @@ def torch_photometric_loss(image, target, window, ssim_weight=0.2):
     c1, c2 = 0.01 ** 2, 0.03 ** 2
     ssim = (((2 * mu_x * mu_y + c1) * (2 * cov + c2)) / ((mu_x * mu_x + mu_y * mu_y + c1) * (var_x + var_y + c2))).mean()
     return (1 - ssim_weight) * (image - target).abs().mean() + ssim_weight * (1 - ssim)
+
+
+def map_masked_loss(image, target, mask, ssim_weight=0.2):
+    """the masked loss from the operators without mask=: the SSIM map weighted in torch, and a torch L1"""
+    w = mask.unsqueeze(-1)
+    norm = image.shape[-1] * mask.sum()
+    ssim_mean = (ssim(image, target, reduction="none") * w).sum() / norm
+    l1 = ((image - target).abs() * w).sum() / norm
+    return (1 - ssim_weight) * l1 + ssim_weight * (1 - ssim_mean)
+
+
+def _mask(args):
+    w, h = args.image_size
+    return torch.rand(h, w, generator=torch.Generator().manual_seed(args.seed + 1)).to(args.device)
 
 
 def _inputs(args):
@@ -78,11 +94,23 @@ def bench_loss(args):
         image.grad = None
         photometric_loss(image, target, ssim_weight=0.0).backward()
 
+    mask = _mask(args)
+
+    def fused_masked():
+        image.grad = None
+        photometric_loss(image, target, ssim_weight=args.ssim_weight, mask=mask).backward()
+
+    def map_masked():
+        image.grad = None
+        map_masked_loss(image, target, mask, args.ssim_weight).backward()
+
     with torch.no_grad():
         phases.run("fused forward", forward)
     phases.run("fused forward+backward", fused)
     phases.run("torch forward+backward", composed)
     phases.run("l1 only", l1_only)
+    phases.run("fused masked forward+backward", fused_masked)
+    phases.run("map + torch masked forward+backward", map_masked)
     elements = image.numel()
     for name, nbytes in (("fused forward", BYTES_FWD), ("fused forward+backward", BYTES_FWD_BWD)):
         ms = phases.results[name]

@@ -36,6 +36,14 @@
 //
 // The scalars are deterministic: every workgroup writes its two partial sums (double) to scratch and one small
 // launch adds them in a fixed order.  No float atomics anywhere.
+//
+// Per-pixel weights (the gs_photo_loss_weighted_* entry points): w(b, p) >= 0, one per pixel, shared by the channels,
+// weights both means and leaves the map alone:  L = sum w |x - y| / (C S),  M = sum_counted w m / (C S_v),  S = sum w,
+// S_v = sum of w over the counted pixels.  The forward multiplies w(p) into its two sums at the output pixel; the
+// workgroups of channel group 0 also write sum w and sum counted w of their tile, and the finish launch divides by
+// C S and C S_v.  The backward multiplies the mean's upstream by w(q) at the halo pixel q and the L1 term by w(p), and
+// reads S, S_v from device memory as the forward left them.  A term whose weight sum is zero gives 0 to the loss and
+// to the gradient, and NaN as its part.  WT = false compiles the unweighted kernels as they were.
 
 #include <cmath>
 
@@ -58,6 +66,12 @@ struct LossImage {
 };
 
 template <typename T>
+struct LossWeight {
+  const T* p;          // one weight per pixel
+  int64_t sb, sr, sp;  // batch (0 = the same weights for every batch entry) / row / pixel stride in elements
+};
+
+template <typename T>
 struct LossWindow {
   T w[LOSS_MAX_WS];
   T d;  // 1 - (sum of w)^2, formed in double
@@ -75,6 +89,8 @@ struct LossFwdArgs {
   T* saved;     // 3 x (B,H,W,C): A', D, C; or null
   int64_t plane;  // B*H*W*C
   double* partials;  // 2 per workgroup: sum |x - y|, sum of the (masked) ssim map
+  LossWeight<T> w;    // the weighted kernels only
+  double* wpartials;  // 2 per pixel tile and batch entry: sum w, sum of the counted w
 };
 
 template <typename T>
@@ -89,6 +105,9 @@ struct LossBwdArgs {
   const T* grad;      // device scalar multiplying both coefficients, or null (= 1)
   T l1_coeff, ssim_coeff;  // already divided by the element counts
   T* d_image;         // (B,H,W,C) contiguous
+  LossWeight<T> w;    // the weighted kernels only, which divide the raw coefficients by C S and C S_v themselves
+  const T* norm;      // device [S, S_v] as the weighted forward wrote them
+  double l1_raw, ssim_raw;
 };
 
 template <typename T>
@@ -115,8 +134,36 @@ __device__ __forceinline__ double loss_block_sum(double v, double* s_red, int ti
   return total;
 }
 
+template <typename T>
+__device__ __forceinline__ T loss_weight_at(const LossWeight<T>& w, int b, int gy, int gx) {
+  return w.p[int64_t(b) * w.sb + gy * w.sr + gx * w.sp];
+}
+
+// the tile's sum w and sum of the counted w; channel group 0 alone, as the weights have no channel axis
+template <typename T>
+__device__ __forceinline__ void loss_weight_partials(const LossFwdArgs<T>& a, int b, T w_all, T w_counted,
+                                                     double* s_red, int tid) {
+  const double total = loss_block_sum(double(w_all), s_red, tid);
+  const double counted = loss_block_sum(double(w_counted), s_red, tid);
+  if (tid == 0) {
+    const int64_t tile = (int64_t(b) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    a.wpartials[2 * tile] = total;
+    a.wpartials[2 * tile + 1] = counted;
+  }
+}
+
+// the weighted backward's coefficients: l1_raw / (C S) and ssim_raw / (C S_v) formed in double as the host forms
+// l1_coeff / count, and 0 for a term without weight
+template <typename T>
+__device__ __forceinline__ void loss_weighted_coeffs(const LossBwdArgs<T>& a, T* l1, T* ss) {
+  const double S = double(a.norm[0]), Sv = double(a.norm[1]);
+  *l1 = S > 0.0 ? T(a.l1_raw / (double(a.channels) * S)) : T(0);
+  *ss = Sv > 0.0 ? T(a.ssim_raw / (double(a.channels) * Sv)) : T(0);
+}
+
 // WS: the window size the loops are unrolled for, or 0 = any odd size up to LOSS_MAX_WS (weights read from LDS)
-template <typename T, int WS>
+// WT: per-pixel weights (a.w)
+template <typename T, int WS, bool WT>
 __global__ __launch_bounds__(256) void photo_loss_fwd_kernel(LossFwdArgs<T> a) {
   constexpr int LOSS_CB = loss_cb<T>();
   constexpr int RMAX = WS ? WS / 2 : LOSS_MAX_WS / 2;
@@ -169,6 +216,8 @@ __global__ __launch_bounds__(256) void photo_loss_fwd_kernel(LossFwdArgs<T> a) {
   const bool inside = gy < H && gx < W;
   const bool counted = inside && (!a.valid || (gy >= R && gy < H - R && gx >= R && gx < W - R));
   T l1_sum = T(0), ssim_sum = T(0);
+  T wp = T(0);
+  if (WT && inside) wp = loss_weight_at(a.w, b, gy, gx);
 
   for (int ch = 0; ch < nc; ++ch) {
     const T* hx = s_halo + ch * 2 * PLANE;
@@ -206,10 +255,10 @@ __global__ __launch_bounds__(256) void photo_loss_fwd_kernel(LossFwdArgs<T> a) {
     const T b1 = mux * mux + muy * muy + a.c1, b2 = T(2) * (varx - covxd) + vard + a.c2;
     const T p = mud * mud / b1, q = vard / b2;
     const T P = T(1) - p, Q = T(1) - q, m = P * Q;
-    if (counted) ssim_sum += m;
+    if (counted) ssim_sum += WT ? wp * m : m;
     if (inside) {
       const T xv = xb[gy * a.x.sr + gx * a.x.sp + ch], yv = yb[gy * a.y.sr + gx * a.y.sp + ch];
-      l1_sum += loss_abs(xv - yv);
+      l1_sum += WT ? wp * loss_abs(xv - yv) : loss_abs(xv - yv);
     }
     T* stage = s_halo + ch * 2 * PLANE;
     stage[tid] = m;
@@ -245,10 +294,11 @@ __global__ __launch_bounds__(256) void photo_loss_fwd_kernel(LossFwdArgs<T> a) {
     a.partials[2 * wg] = l1_total;
     a.partials[2 * wg + 1] = ssim_total;
   }
+  if (WT && c0 == 0) loss_weight_partials(a, b, wp, counted ? wp : T(0), s_red, tid);
 }
 
 // ssim_weight = 0: the same grid and partials, nothing but |x - y|
-template <typename T>
+template <typename T, bool WT>
 __global__ __launch_bounds__(256) void photo_loss_l1_fwd_kernel(LossFwdArgs<T> a) {
   constexpr int LOSS_CB = loss_cb<T>();
   __shared__ double s_red[4];
@@ -261,8 +311,10 @@ __global__ __launch_bounds__(256) void photo_loss_l1_fwd_kernel(LossFwdArgs<T> a
   T l1_sum = T(0);
   for (int i = tid; i < 256 * nc; i += 256) {
     const int ch = i % nc, p = i / nc, gy = y0 + (p / LOSS_T), gx = x0 + (p % LOSS_T);
-    if (gy < a.height && gx < a.width)
-      l1_sum += loss_abs(xb[gy * a.x.sr + gx * a.x.sp + ch] - yb[gy * a.y.sr + gx * a.y.sp + ch]);
+    if (gy < a.height && gx < a.width) {
+      const T v = loss_abs(xb[gy * a.x.sr + gx * a.x.sp + ch] - yb[gy * a.y.sr + gx * a.y.sp + ch]);
+      l1_sum += WT ? loss_weight_at(a.w, b, gy, gx) * v : v;
+    }
   }
   const double total = loss_block_sum(double(l1_sum), s_red, tid);
   if (tid == 0) {
@@ -270,13 +322,23 @@ __global__ __launch_bounds__(256) void photo_loss_l1_fwd_kernel(LossFwdArgs<T> a
     a.partials[2 * wg] = total;
     a.partials[2 * wg + 1] = 0.0;
   }
+  if (WT && c0 == 0) {
+    const int gy = y0 + tid / LOSS_T, gx = x0 + tid % LOSS_T, R = a.win.ws >> 1;
+    const bool inside = gy < a.height && gx < a.width;
+    const bool counted = inside && (!a.valid || (gy >= R && gy < a.height - R && gx >= R && gx < a.width - R));
+    const T wp = inside ? loss_weight_at(a.w, b, gy, gx) : T(0);
+    loss_weight_partials(a, b, wp, counted ? wp : T(0), s_red, tid);
+  }
 }
 
-// one workgroup: the partials in a fixed order, in double; results = [loss, l1_mean, ssim_mean]
+// one workgroup: the partials in a fixed order, in double; results = [loss, l1_mean, ssim_mean], and with nres == 5 also
+// [S, S_v].  wpartials (nw pairs) or null: the weight sums that replace the host's counts, count = channels * sum.  A
+// weighted term with no weight adds nothing to the loss and reports NaN.
 template <typename T>
 __global__ __launch_bounds__(256) void photo_loss_finish_kernel(const double* partials, int64_t n, double count_l1,
                                                                double count_ssim, double ssim_weight, int do_ssim,
-                                                               T* results) {
+                                                               const double* wpartials, int64_t nw, double channels,
+                                                               int nres, T* results) {
   __shared__ double s_l1[256], s_ss[256];
   const int tid = threadIdx.x;
   double l1 = 0.0, ss = 0.0;
@@ -287,17 +349,37 @@ __global__ __launch_bounds__(256) void photo_loss_finish_kernel(const double* pa
     if (tid < half) { s_l1[tid] += s_l1[tid + half]; s_ss[tid] += s_ss[tid + half]; }
     __syncthreads();
   }
+  const double l1_total = s_l1[0], ss_total = s_ss[0];
+  double S = count_l1 / channels, Sv = count_ssim / channels;
+  if (wpartials) {
+    __syncthreads();
+    double w = 0.0, wv = 0.0;
+    for (int64_t i = tid; i < nw; i += 256) { w += wpartials[2 * i]; wv += wpartials[2 * i + 1]; }
+    s_l1[tid] = w; s_ss[tid] = wv;
+    __syncthreads();
+    for (int half = 128; half >= 1; half >>= 1) {
+      if (tid < half) { s_l1[tid] += s_l1[tid + half]; s_ss[tid] += s_ss[tid + half]; }
+      __syncthreads();
+    }
+    S = s_l1[0]; Sv = s_ss[0];
+    count_l1 = channels * S; count_ssim = channels * Sv;
+  }
   if (tid == 0) {
-    const double l1_mean = s_l1[0] / count_l1;
-    const double ssim_mean = do_ssim ? s_ss[0] / count_ssim : nan("");
-    results[0] = T(do_ssim ? (1.0 - ssim_weight) * l1_mean + ssim_weight * (1.0 - ssim_mean)
-                           : (1.0 - ssim_weight) * l1_mean);
+    const bool has_l1 = !wpartials || S > 0.0, has_ssim = do_ssim && (!wpartials || Sv > 0.0);
+    const double l1_mean = has_l1 ? l1_total / count_l1 : nan("");
+    const double ssim_mean = has_ssim ? ss_total / count_ssim : nan("");
+    double loss = 0.0;
+    if (has_l1 && has_ssim) loss = (1.0 - ssim_weight) * l1_mean + ssim_weight * (1.0 - ssim_mean);
+    else if (has_l1) loss = (1.0 - ssim_weight) * l1_mean;
+    else if (has_ssim) loss = ssim_weight * (1.0 - ssim_mean);
+    results[0] = T(loss);
     results[1] = T(l1_mean);
     results[2] = T(ssim_mean);
+    if (nres == 5) { results[3] = T(S); results[4] = T(Sv); }
   }
 }
 
-template <typename T, int WS>
+template <typename T, int WS, bool WT>
 __global__ __launch_bounds__(256) void photo_loss_bwd_kernel(LossBwdArgs<T> a) {
   constexpr int LOSS_CB = loss_cb<T>();
   constexpr int RMAX = WS ? WS / 2 : LOSS_MAX_WS / 2;
@@ -316,7 +398,9 @@ __global__ __launch_bounds__(256) void photo_loss_bwd_kernel(LossBwdArgs<T> a) {
   const T* xb = a.x.p + int64_t(b) * a.x.sb + c0;
   const T* yb = a.y.p + int64_t(b) * a.y.sb + c0;
   const T gl = a.grad ? a.grad[0] : T(1);
-  const T u_mean = a.ssim_coeff * gl;
+  T l1_coeff = a.l1_coeff, ssim_coeff = a.ssim_coeff;
+  if (WT) loss_weighted_coeffs(a, &l1_coeff, &ssim_coeff);
+  const T u_mean = ssim_coeff * gl;
 
   loss_stage_window(a.win, s_w, tid);
   if (tid < 18 * nc) {
@@ -337,7 +421,9 @@ __global__ __launch_bounds__(256) void photo_loss_bwd_kernel(LossBwdArgs<T> a) {
     if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
       const int64_t at = ((int64_t(b) * H + gy) * W + gx) * a.channels + c0 + ch;
       T u = T(0);
-      if (!a.valid || (gy >= R && gy < H - R && gx >= R && gx < W - R)) u = u_mean;
+      // one weight per halo pixel: the lanes of its channels read the same address
+      if (!a.valid || (gy >= R && gy < H - R && gx >= R && gx < W - R))
+        u = WT ? u_mean * loss_weight_at(a.w, b, gy, gx) : u_mean;
       if (a.upstream) u += a.upstream[at];
       const T A = a.saved[at], Dq = a.saved[a.plane + at], Cq = a.saved[2 * a.plane + at];
       const int t = ((gy >> 4) - int(blockIdx.y) + 1) * 3 + ((gx >> 4) - int(blockIdx.x) + 1);
@@ -359,7 +445,8 @@ __global__ __launch_bounds__(256) void photo_loss_bwd_kernel(LossBwdArgs<T> a) {
 
   const int gy = y0 + ty, gx = x0 + tx;
   const bool inside = gy < H && gx < W;
-  const T u_l1 = a.l1_coeff * gl;
+  T u_l1 = l1_coeff * gl;
+  if (WT && inside) u_l1 *= loss_weight_at(a.w, b, gy, gx);
 
   for (int ch = 0; ch < nc; ++ch) {
     const T* ha = s_halo + ch * 3 * PLANE;
@@ -403,7 +490,7 @@ __global__ __launch_bounds__(256) void photo_loss_bwd_kernel(LossBwdArgs<T> a) {
 }
 
 // no SSIM term: d_image = coefficient * sign(x - y)
-template <typename T>
+template <typename T, bool WT>
 __global__ __launch_bounds__(256) void photo_loss_l1_bwd_kernel(LossBwdArgs<T> a) {
   constexpr int LOSS_CB = loss_cb<T>();
   const int tid = threadIdx.x;
@@ -412,10 +499,13 @@ __global__ __launch_bounds__(256) void photo_loss_l1_bwd_kernel(LossBwdArgs<T> a
   const int x0 = blockIdx.x * LOSS_T, y0 = blockIdx.y * LOSS_T;
   const T* xb = a.x.p + int64_t(b) * a.x.sb + c0;
   const T* yb = a.y.p + int64_t(b) * a.y.sb + c0;
-  const T u_l1 = a.l1_coeff * (a.grad ? a.grad[0] : T(1));
+  T l1_coeff = a.l1_coeff, ssim_coeff = a.ssim_coeff;
+  if (WT) loss_weighted_coeffs(a, &l1_coeff, &ssim_coeff);
+  const T u_tile = l1_coeff * (a.grad ? a.grad[0] : T(1));
   for (int i = tid; i < 256 * nc; i += 256) {
     const int ch = i % nc, p = i / nc, gy = y0 + (p / LOSS_T), gx = x0 + (p % LOSS_T);
     if (gy >= a.height || gx >= a.width) continue;
+    const T u_l1 = WT ? u_tile * loss_weight_at(a.w, b, gy, gx) : u_tile;
     const T diff = xb[gy * a.x.sr + gx * a.x.sp + ch] - yb[gy * a.y.sr + gx * a.y.sp + ch];
     a.d_image[((int64_t(b) * a.height + gy) * a.width + gx) * a.channels + c0 + ch] =
         diff > T(0) ? u_l1 : (diff < T(0) ? -u_l1 : T(0));
@@ -485,6 +575,28 @@ int loss_image(const char* who, const char* name, const LossShape& s, const T* p
   return GS_OK;
 }
 
+// what a weighted entry point adds to the unweighted argument list; weight == NULL runs unweighted
+template <typename T>
+struct LossWeighted {
+  const T* weight;
+  int64_t sb, sr, sp;
+  const T* norm;  // backward: device [S, S_v]
+};
+
+template <typename T>
+int loss_weight(const char* who, const LossShape& s, const LossWeighted<T>& wt, LossWeight<T>* out) {
+  GS_REQUIRE(wt.sp >= 1 && wt.sr >= s.width * wt.sp && (wt.sb == 0 || wt.sb >= s.height * wt.sr),
+             GS_ERR_INVALID_ARGUMENT,
+             "%s: bad strides of weight (batch %lld, row %lld, pixel %lld elements for %lld x %lld; batch 0 = broadcast)",
+             who, (long long)wt.sb, (long long)wt.sr, (long long)wt.sp, (long long)s.height, (long long)s.width);
+  out->p = wt.weight; out->sb = wt.sb; out->sr = wt.sr; out->sp = wt.sp;
+  return GS_OK;
+}
+
+int64_t loss_tiles(int64_t batch, int64_t height, int64_t width) {
+  return batch * gs_div_up(width, LOSS_T) * gs_div_up(height, LOSS_T);
+}
+
 #define LOSS_TRY(expr)          \
   do {                          \
     const int rc_ = (expr);     \
@@ -495,7 +607,8 @@ template <typename T>
 int loss_fwd(const char* who, int64_t batch, int64_t height, int64_t width, int64_t channels, const T* image,
              int64_t isb, int64_t isr, int64_t isp, const T* target, int64_t tsb, int64_t tsr, int64_t tsp,
              int32_t ws, double sigma, double data_range, double ssim_weight, int32_t valid, T* ssim_map,
-             T* saved_maps, void* scratch, int64_t scratch_bytes, T* results, void* stream) {
+             T* saved_maps, void* scratch, int64_t scratch_bytes, T* results, void* stream,
+             const LossWeighted<T>* wt = nullptr) {
   LossShape s;
   LossFwdArgs<T> a;
   LOSS_TRY(loss_shape(who, loss_cb<T>(), batch, height, width, channels, &s));
@@ -509,11 +622,15 @@ int loss_fwd(const char* who, int64_t batch, int64_t height, int64_t width, int6
              (long long)width);
   LOSS_TRY(loss_image(who, "image", s, image, isb, isr, isp, &a.x));
   LOSS_TRY(loss_image(who, "target", s, target, tsb, tsr, tsp, &a.y));
+  const bool weighted = wt && wt->weight;
+  a.w = LossWeight<T>{nullptr, 0, 0, 0};
+  if (weighted) LOSS_TRY(loss_weight(who, s, *wt, &a.w));
   GS_REQUIRE(results != nullptr && scratch != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (results / scratch)",
              who);
   GS_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, GS_ERR_INVALID_ARGUMENT,
              "%s: scratch must be 8-byte aligned", who);
-  const int64_t need = gs_photo_loss_scratch_bytes(batch, height, width, channels);  // one size for both dtypes
+  const int64_t unweighted_need = gs_photo_loss_scratch_bytes(batch, height, width, channels);  // one size for both dtypes
+  const int64_t need = wt ? gs_photo_loss_weighted_scratch_bytes(batch, height, width, channels) : unweighted_need;
   GS_REQUIRE(scratch_bytes >= need, GS_ERR_SCRATCH_TOO_SMALL, "%s: scratch %lld < %lld bytes", who,
              (long long)scratch_bytes, (long long)need);
   a.batch = int(batch); a.height = int(height); a.width = int(width); a.channels = int(channels);
@@ -525,17 +642,25 @@ int loss_fwd(const char* who, int64_t batch, int64_t height, int64_t width, int6
   a.map = ssim_map; a.saved = saved_maps;
   a.plane = batch * height * width * channels;
   a.partials = static_cast<double*>(scratch);
+  a.wpartials = weighted ? reinterpret_cast<double*>(static_cast<char*>(scratch) + unweighted_need) : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(unsigned(s.tiles_x), unsigned(s.tiles_y), unsigned(batch * s.chunks));
-  if (!a.do_ssim) hipLaunchKernelGGL(photo_loss_l1_fwd_kernel<T>, grid, dim3(256), 0, st, a);
-  else if (ws == 11) hipLaunchKernelGGL((photo_loss_fwd_kernel<T, 11>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((photo_loss_fwd_kernel<T, 0>), grid, dim3(256), 0, st, a);
+  if (weighted) {
+    if (!a.do_ssim) hipLaunchKernelGGL((photo_loss_l1_fwd_kernel<T, true>), grid, dim3(256), 0, st, a);
+    else if (ws == 11) hipLaunchKernelGGL((photo_loss_fwd_kernel<T, 11, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((photo_loss_fwd_kernel<T, 0, true>), grid, dim3(256), 0, st, a);
+  } else {
+    if (!a.do_ssim) hipLaunchKernelGGL((photo_loss_l1_fwd_kernel<T, false>), grid, dim3(256), 0, st, a);
+    else if (ws == 11) hipLaunchKernelGGL((photo_loss_fwd_kernel<T, 11, false>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((photo_loss_fwd_kernel<T, 0, false>), grid, dim3(256), 0, st, a);
+  }
   GS_CHECK_LAUNCH(who);
   const double count = double(a.plane);
   const double count_ssim =
       valid ? double(batch) * double(height - ws + 1) * double(width - ws + 1) * double(channels) : count;
   hipLaunchKernelGGL(photo_loss_finish_kernel<T>, dim3(1), dim3(256), 0, st, a.partials, s.groups, count, count_ssim,
-                     ssim_weight, a.do_ssim, results);
+                     ssim_weight, a.do_ssim, a.wpartials, loss_tiles(batch, height, width), double(channels),
+                     wt ? 5 : 3, results);
   GS_CHECK_LAUNCH(who);
   return GS_OK;
 }
@@ -544,7 +669,7 @@ template <typename T>
 int loss_bwd(const char* who, int64_t batch, int64_t height, int64_t width, int64_t channels, const T* image,
              int64_t isb, int64_t isr, int64_t isp, const T* target, int64_t tsb, int64_t tsr, int64_t tsp,
              int32_t ws, double sigma, int32_t valid, const T* saved_maps, const T* upstream_map, const T* grad_loss,
-             double l1_coeff, double ssim_coeff, T* d_image, void* stream) {
+             double l1_coeff, double ssim_coeff, T* d_image, void* stream, const LossWeighted<T>* wt = nullptr) {
   LossShape s;
   LossBwdArgs<T> a;
   LOSS_TRY(loss_shape(who, loss_cb<T>(), batch, height, width, channels, &s));
@@ -557,9 +682,15 @@ int loss_bwd(const char* who, int64_t batch, int64_t height, int64_t width, int6
              (long long)width);
   LOSS_TRY(loss_image(who, "image", s, image, isb, isr, isp, &a.x));
   LOSS_TRY(loss_image(who, "target", s, target, tsb, tsr, tsp, &a.y));
+  const bool weighted = wt && wt->weight;
+  a.w = LossWeight<T>{nullptr, 0, 0, 0};
+  if (weighted) LOSS_TRY(loss_weight(who, s, *wt, &a.w));
   const bool do_ssim = ssim_coeff != 0.0 || upstream_map != nullptr;
   GS_REQUIRE(d_image != nullptr && (!do_ssim || saved_maps != nullptr), GS_ERR_INVALID_ARGUMENT,
              "%s: NULL buffer (d_image / saved_maps)", who);
+  GS_REQUIRE(!wt || wt->norm != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (normalisers)", who);
+  a.norm = wt ? wt->norm : nullptr;
+  a.l1_raw = l1_coeff; a.ssim_raw = ssim_coeff;
   a.batch = int(batch); a.height = int(height); a.width = int(width); a.channels = int(channels);
   a.chunks = int(s.chunks);
   a.valid = valid ? 1 : 0;
@@ -573,9 +704,15 @@ int loss_bwd(const char* who, int64_t batch, int64_t height, int64_t width, int6
   a.d_image = d_image;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(unsigned(s.tiles_x), unsigned(s.tiles_y), unsigned(batch * s.chunks));
-  if (!do_ssim) hipLaunchKernelGGL(photo_loss_l1_bwd_kernel<T>, grid, dim3(256), 0, st, a);
-  else if (ws == 11) hipLaunchKernelGGL((photo_loss_bwd_kernel<T, 11>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((photo_loss_bwd_kernel<T, 0>), grid, dim3(256), 0, st, a);
+  if (weighted) {
+    if (!do_ssim) hipLaunchKernelGGL((photo_loss_l1_bwd_kernel<T, true>), grid, dim3(256), 0, st, a);
+    else if (ws == 11) hipLaunchKernelGGL((photo_loss_bwd_kernel<T, 11, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((photo_loss_bwd_kernel<T, 0, true>), grid, dim3(256), 0, st, a);
+  } else {
+    if (!do_ssim) hipLaunchKernelGGL((photo_loss_l1_bwd_kernel<T, false>), grid, dim3(256), 0, st, a);
+    else if (ws == 11) hipLaunchKernelGGL((photo_loss_bwd_kernel<T, 11, false>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((photo_loss_bwd_kernel<T, 0, false>), grid, dim3(256), 0, st, a);
+  }
   GS_CHECK_LAUNCH(who);
   return GS_OK;
 }
@@ -644,4 +781,77 @@ extern "C" int gs_photo_loss_bwd_f64(int64_t batch, int64_t height, int64_t widt
                           image_row_stride, image_pixel_stride, target, target_batch_stride, target_row_stride,
                           target_pixel_stride, window_size, sigma, valid, saved_maps, upstream_map, grad_loss,
                           l1_coeff, ssim_coeff, d_image, stream);
+}
+
+extern "C" int64_t gs_photo_loss_weighted_scratch_bytes(int64_t batch, int64_t height, int64_t width,
+                                                        int64_t channels) {
+  if (batch < 0 || height < 0 || width < 0 || channels < 1) return 0;
+  return gs_photo_loss_scratch_bytes(batch, height, width, channels) + loss_tiles(batch, height, width) * 16;
+}
+
+extern "C" int gs_photo_loss_weighted_fwd(int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                          const float* image, int64_t image_batch_stride, int64_t image_row_stride,
+                                          int64_t image_pixel_stride, const float* target, int64_t target_batch_stride,
+                                          int64_t target_row_stride, int64_t target_pixel_stride,
+                                          const float* weight, int64_t weight_batch_stride, int64_t weight_row_stride,
+                                          int64_t weight_pixel_stride, int32_t window_size, double sigma,
+                                          double data_range, double ssim_weight, int32_t valid, float* ssim_map,
+                                          float* saved_maps, void* scratch, int64_t scratch_bytes, float* results,
+                                          void* stream) {
+  const LossWeighted<float> wt{weight, weight_batch_stride, weight_row_stride, weight_pixel_stride, nullptr};
+  return loss_fwd<float>("gs_photo_loss_weighted_fwd", batch, height, width, channels, image, image_batch_stride,
+                         image_row_stride, image_pixel_stride, target, target_batch_stride, target_row_stride,
+                         target_pixel_stride, window_size, sigma, data_range, ssim_weight, valid, ssim_map, saved_maps,
+                         scratch, scratch_bytes, results, stream, &wt);
+}
+
+extern "C" int gs_photo_loss_weighted_fwd_f64(int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                              const double* image, int64_t image_batch_stride,
+                                              int64_t image_row_stride, int64_t image_pixel_stride,
+                                              const double* target, int64_t target_batch_stride,
+                                              int64_t target_row_stride, int64_t target_pixel_stride,
+                                              const double* weight, int64_t weight_batch_stride,
+                                              int64_t weight_row_stride, int64_t weight_pixel_stride,
+                                              int32_t window_size, double sigma, double data_range, double ssim_weight,
+                                              int32_t valid, double* ssim_map, double* saved_maps, void* scratch,
+                                              int64_t scratch_bytes, double* results, void* stream) {
+  const LossWeighted<double> wt{weight, weight_batch_stride, weight_row_stride, weight_pixel_stride, nullptr};
+  return loss_fwd<double>("gs_photo_loss_weighted_fwd_f64", batch, height, width, channels, image, image_batch_stride,
+                          image_row_stride, image_pixel_stride, target, target_batch_stride, target_row_stride,
+                          target_pixel_stride, window_size, sigma, data_range, ssim_weight, valid, ssim_map,
+                          saved_maps, scratch, scratch_bytes, results, stream, &wt);
+}
+
+extern "C" int gs_photo_loss_weighted_bwd(int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                          const float* image, int64_t image_batch_stride, int64_t image_row_stride,
+                                          int64_t image_pixel_stride, const float* target, int64_t target_batch_stride,
+                                          int64_t target_row_stride, int64_t target_pixel_stride,
+                                          const float* weight, int64_t weight_batch_stride, int64_t weight_row_stride,
+                                          int64_t weight_pixel_stride, const float* normalisers, int32_t window_size,
+                                          double sigma, int32_t valid, const float* saved_maps,
+                                          const float* upstream_map, const float* grad_loss, double l1_coeff,
+                                          double ssim_coeff, float* d_image, void* stream) {
+  const LossWeighted<float> wt{weight, weight_batch_stride, weight_row_stride, weight_pixel_stride, normalisers};
+  return loss_bwd<float>("gs_photo_loss_weighted_bwd", batch, height, width, channels, image, image_batch_stride,
+                         image_row_stride, image_pixel_stride, target, target_batch_stride, target_row_stride,
+                         target_pixel_stride, window_size, sigma, valid, saved_maps, upstream_map, grad_loss, l1_coeff,
+                         ssim_coeff, d_image, stream, &wt);
+}
+
+extern "C" int gs_photo_loss_weighted_bwd_f64(int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                              const double* image, int64_t image_batch_stride,
+                                              int64_t image_row_stride, int64_t image_pixel_stride,
+                                              const double* target, int64_t target_batch_stride,
+                                              int64_t target_row_stride, int64_t target_pixel_stride,
+                                              const double* weight, int64_t weight_batch_stride,
+                                              int64_t weight_row_stride, int64_t weight_pixel_stride,
+                                              const double* normalisers, int32_t window_size, double sigma,
+                                              int32_t valid, const double* saved_maps, const double* upstream_map,
+                                              const double* grad_loss, double l1_coeff, double ssim_coeff,
+                                              double* d_image, void* stream) {
+  const LossWeighted<double> wt{weight, weight_batch_stride, weight_row_stride, weight_pixel_stride, normalisers};
+  return loss_bwd<double>("gs_photo_loss_weighted_bwd_f64", batch, height, width, channels, image, image_batch_stride,
+                          image_row_stride, image_pixel_stride, target, target_batch_stride, target_row_stride,
+                          target_pixel_stride, window_size, sigma, valid, saved_maps, upstream_map, grad_loss,
+                          l1_coeff, ssim_coeff, d_image, stream, &wt);
 }
