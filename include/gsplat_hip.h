@@ -596,6 +596,38 @@ int64_t gs_rows_union_scratch_bytes(int64_t n);
 int gs_rows_union(int64_t n, int64_t count, const int64_t* rows, int64_t* union_rows, int32_t* union_count,
                   void* scratch, int64_t scratch_bytes, void* stream);
 
+/* A batch of views taken as a batch (render_views): every view's frame holds slot_of (n int32: the compact row of
+ * Gaussian i in that view, negative = not in view; GsFrameLayout.slot_of), which is what the two entry points above
+ * search for.  Up to GS_VIEWS_MAX views; an empty call (n == 0, rows == 0, views == 0) writes nothing and returns 0,
+ * except gs_views_sum_rows with views == 0 and rows > 0, which writes zeros. */
+#define GS_VIEWS_MAX 16
+
+/* ascending distinct union of the views: row r is listed iff slot_of[r] >= 0 in some view.  slot_of_host: a HOST array
+ * of `views` device pointers.  One streaming pass over the tables (4 * views * n bytes) builds the bitmap without
+ * atomics; scan and emit as gs_rows_union.  union_rows: room for the union (n rows, or the sum of the views' visible
+ * counts, always suffice); *union_count on the device.  scratch: 16-byte aligned.  n < 2^31. */
+int64_t gs_views_union_scratch_bytes(int64_t n);
+int gs_views_union(int64_t n, int32_t views, const int32_t* const* slot_of_host, int64_t* union_rows,
+                   int32_t* union_count, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* one view's row-compact values: row slot_of[i] of `values` (count rows, `stride` >= dims floats apart) belongs to
+ * Gaussian i */
+typedef struct GsViewRows {
+  const int32_t* slot_of;
+  const float* values;
+  int64_t count;
+  int32_t stride;
+} GsViewRows;
+
+/* out (rows, dims) = for each indexes[i] the sum over the views, IN VIEW ORDER from 0.0f, of
+ * values_b[slot_of_b[indexes[i]] * stride_b + 0 .. dims); a view whose slot is < 0 or >= count_b is skipped (nothing
+ * is read behind a view's values), a view with count 0 is never read.  The arithmetic of the sequential
+ * acc[rows_b] += values_b: the same bits on every call.  view_rows_host: a HOST array of `views` entries, passed to
+ * the kernel by value.  indexes[i] must lie inside the tables (negative entries give zeros).  16-byte accesses when
+ * dims and every stride are multiples of 4 floats and every values pointer and `out` are 16-byte aligned. */
+int gs_views_sum_rows(int64_t rows, const int64_t* indexes, int32_t views, const GsViewRows* view_rows_host,
+                      int32_t dims, float* out, void* stream);
+
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
  * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are

@@ -10,7 +10,7 @@ from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
 from .perspective import CameraParams
 from .rasterizer import RasterOut, rasterize, rasterize_with_tiles
-from .renderer import Rendering, render_gaussians
+from .renderer import RenderedViews, Rendering, render_gaussians, render_views
 from .spherical_harmonics import evaluate_sh_at
 from .taichi_queue import TaichiQueue, taichi_queue
 
@@ -35,7 +35,7 @@ def install_as_taichi_splatting():
 
 
 __all__ = [
-    'render_gaussians', 'Rendering',
+    'render_gaussians', 'Rendering', 'render_views', 'RenderedViews',
     'map_to_tiles', 'pad_to_tile',
     'Gaussians2D', 'Gaussians3D',
     'RasterConfig', 'CameraParams', 'RasterOut',

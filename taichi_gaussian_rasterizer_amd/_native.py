@@ -72,6 +72,14 @@ class GsFrameBwdPart(ctypes.Structure):
                 ("row_begin", c_int64), ("row_end", c_int64)]
 
 
+class GsViewRows(ctypes.Structure):
+    """include/gsplat_hip.h GsViewRows: one view's slot_of table and row-compact values for gs_views_sum_rows"""
+    _fields_ = [("slot_of", c_void_p), ("values", c_void_p), ("count", c_int64), ("stride", c_int32)]
+
+
+GS_VIEWS_MAX = 16  # include/gsplat_hip.h
+
+
 # Developer tuning aids (tools/exp_*.py, the wave-region tests): passed per call inside GsRasterConfig; the
 # library itself reads no environment variable.  GS_RASTER_NB / GS_RASTER_HEAVY seed them at import.
 TUNING = {"wave_sub_blocks": int(os.environ.get("GS_RASTER_NB", "0") or 0),
@@ -160,6 +168,10 @@ SIGNATURES = {
     "gs_rows_sum_runs": (ctypes.c_int, [_I64, _P, _I32, _P, _I64, _P, _I32, _P, _P, _P]),
     "gs_rows_union_scratch_bytes": (_I64, [_I64]),
     "gs_rows_union": (ctypes.c_int, [_I64, _I64, _P, _P, _P, _P, _I64, _P]),
+    # a batch of views as a batch: the union and the sums from the frames' slot_of tables
+    "gs_views_union_scratch_bytes": (_I64, [_I64]),
+    "gs_views_union": (ctypes.c_int, [_I64, _I32, POINTER(c_void_p), _P, _P, _P, _I64, _P]),
+    "gs_views_sum_rows": (ctypes.c_int, [_I64, _P, _I32, POINTER(GsViewRows), _I32, _P, _P]),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),

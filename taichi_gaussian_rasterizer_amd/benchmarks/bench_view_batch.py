@@ -1,11 +1,12 @@
 """One training iteration over a BATCH of views -- zero_grad, B x (render_gaussians(sparse_grad=True), photometric_loss,
 backward) into the same leaves, visible_union, one VisibilityAwareAdam.step -- with the summed gradients read run by
 run (optim.fractional.MERGE_RUNS = True: gs_rows_union, gs_rows_find_runs, gs_rows_sum_runs) against the path through
-torch.unique and coalesce() (MERGE_RUNS = False).
+torch.unique and coalesce() (MERGE_RUNS = False), and against the batch taken as a batch (mode "render_views": one
+render_views node, one backward of the summed losses, opt.step(*views.visible) on the merged gradient).
 
 Scenes as in bench_train_step: the C3 frame (1 M Gaussians, 2048x2048, SH degree 3) and the same frame plus three times
 as many Gaussians behind the camera, rows shuffled.  Batch sizes 2 and 4; the cameras are the benchmark camera moved
-sideways, so that the visible sets differ; the record holds every V_b and the size of the union.  The two modes are
+sideways, so that the visible sets differ; the record holds every V_b and the size of the union.  The three modes are
 timed alternating, round by round: 5 warm-up iterations, 3 rounds of `--iters` (30), median of the round medians, spread
 = largest minus smallest round median.  Timed separately: the whole iteration, and the step alone (visible_union +
 opt.step between two events).
@@ -18,7 +19,7 @@ import statistics
 
 import torch
 
-from .. import render_gaussians
+from .. import render_gaussians, render_views
 from ..data_types import Gaussians3D, RasterConfig
 from ..losses import photometric_loss
 from ..optim import VisibilityAwareAdam, fractional, visible_union
@@ -54,10 +55,21 @@ class BatchTrainer:
         self.targets = [torch.rand(h, w, 3, generator=gen).to(device) for _ in self.cams]
         self.visible, self.union = [], 0
 
-    def iteration(self, merge: bool, step_events=None):
-        fractional.MERGE_RUNS = merge
+    def iteration(self, merge, step_events=None):
+        """merge: the value of MERGE_RUNS for the view-by-view iteration; None: the iteration through render_views"""
         self.opt.zero_grad()
         g = Gaussians3D(**self.params, batch_size=(self.n,))
+        if merge is None:
+            views = render_views(g, self.cams, self.cfg, use_sh=True)
+            sum(photometric_loss(r.image, target) for r, target in zip(views, self.targets)).backward()
+            if step_events is not None:
+                step_events[0].record()
+            self.opt.step(*views.visible)
+            if step_events is not None:
+                step_events[1].record()
+            self.visible, self.union = [r.num_points for r in views], views.num_points
+            return
+        fractional.MERGE_RUNS = merge
         rs = [render_gaussians(g, cam, self.cfg, use_sh=True, sparse_grad=True) for cam in self.cams]
         for r, target in zip(rs, self.targets):
             photometric_loss(r.image, target).backward()
@@ -90,7 +102,7 @@ def _summary(rounds):
 
 
 def bench_batch(args, g, cam, batch: int, warmup=5, rounds=3):
-    modes = {"coalesce": False, "merge_runs": True}
+    modes = {"coalesce": False, "merge_runs": True, "render_views": None}
     trainers = {name: BatchTrainer(g, cam, args.device, batch) for name in modes}
     whole = {name: [] for name in modes}
     step = {name: [] for name in modes}
@@ -114,10 +126,14 @@ def bench_batch(args, g, cam, batch: int, warmup=5, rounds=3):
     a, b = out["coalesce"], out["merge_runs"]
     out["step_faster"] = a["step"]["ms"] - b["step"]["ms"] > max(a["step"]["spread_ms"], b["step"]["spread_ms"])
     out["iteration_not_slower"] = b["iteration"]["ms"] - a["iteration"]["ms"] <= a["iteration"]["spread_ms"]
+    c = out["render_views"]
+    out["render_views_not_slower"] = c["iteration"]["ms"] - b["iteration"]["ms"] <= b["iteration"]["spread_ms"]
     print(f"N = {N}, B = {batch}, V = {t.visible}, union {t.union}: step {a['step']['ms']:.3f} ms coalesce (spread "
           f"{a['step']['spread_ms']:.3f}), {b['step']['ms']:.3f} ms merge_runs (spread {b['step']['spread_ms']:.3f}); "
           f"iteration {a['iteration']['ms']:.3f} (spread {a['iteration']['spread_ms']:.3f}) against "
-          f"{b['iteration']['ms']:.3f} (spread {b['iteration']['spread_ms']:.3f})")
+          f"{b['iteration']['ms']:.3f} (spread {b['iteration']['spread_ms']:.3f}); render_views: step "
+          f"{c['step']['ms']:.3f} ms (spread {c['step']['spread_ms']:.3f}), iteration {c['iteration']['ms']:.3f} "
+          f"(spread {c['iteration']['spread_ms']:.3f})")
     return out
 
 

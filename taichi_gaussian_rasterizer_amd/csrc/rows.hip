@@ -7,6 +7,10 @@
 //               run, then the hit rows added in run order -- a fixed order, so the same bits on every call
 //   union       the ascending distinct union of the views' lists through a bitmap over the N rows
 // Index lists are 8 MB per view at V = 1 M and stay cache-resident under the searches; the value rows are read once.
+// A batch rendered as one node (render_views) has every view's slot_of table (n int32: the compact row of Gaussian i in
+// that view, or -1) and needs neither runs nor searches:
+//   views_union     the same bitmap built from the tables in one streaming pass, without atomics
+//   views_sum_rows  sum_runs with the binary search replaced by one table read per view
 
 #include "gs_common.h"
 
@@ -91,11 +95,45 @@ __device__ __forceinline__ float4 piece_add(float4 a, float4 b) {
   return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
 }
 
+// The second half of a wide-row sum.  A wave holds 64 / RL consecutive output rows from row0 on; lane j * RL + r holds
+// in `hit` the value row that source r (a run, a view) has for the wave's row j, or -1.  The hits are handed around by
+// cross-lane reads: the lanes stride over the (row, piece) pairs of the wave's rows -- a piece is VEC floats, `pieces`
+// of them per row -- load every source's piece and then add the hit ones in source order from zero.  row_of(r, at):
+// the first piece of value row `at` of source r.  Neighbouring lanes read neighbouring pieces of one value row, so a
+// value row is read as one contiguous run of bytes, and the wave's output is one contiguous block.
+template <int RL, int VEC, class RowOf>
+__device__ __forceinline__ void wave_sum_pieces(int hit, int lane, int64_t row0, int64_t rows, int pieces,
+                                                float* out_rows, RowOf row_of) {
+  typedef typename Piece<VEC>::T P;
+  constexpr int RPW = GS_WAVE / RL;                 // rows per wave
+  const int64_t left = rows - row0;
+  const int here = int(left < RPW ? left : RPW);    // rows of this wave
+  const int units = here * pieces;
+  P* out = reinterpret_cast<P*>(out_rows) + row0 * pieces;
+  for (int e0 = 0; e0 < units; e0 += GS_WAVE) {     // wave-uniform trip count: the cross-lane reads see every lane
+    const int e = e0 + lane;
+    const bool live = e < units;
+    const int slot = live ? e / pieces : 0;
+    const int c = e - slot * pieces;
+    P v[RL];
+    int at[RL];
+#pragma unroll
+    for (int r = 0; r < RL; ++r) {
+      at[r] = __shfl(hit, slot * RL + r);
+      if (!live) at[r] = -1;
+      v[r] = piece_zero(P());
+      if (at[r] >= 0) v[r] = row_of(r, at[r])[c];
+    }
+    P acc = piece_zero(P());
+#pragma unroll
+    for (int r = 0; r < RL; ++r)
+      if (at[r] >= 0) acc = piece_add(acc, v[r]);
+    if (live) out[e] = acc;
+  }
+}
+
 // Wide rows.  A wave takes 64 / RL consecutive rows of `indexes`; RL lanes per row (RL >= runs) search one run each, so
-// all searches of the wave's rows proceed side by side.  The hit positions are handed around by cross-lane reads: the
-// lanes then stride over the (row, piece) pairs of the wave's rows -- a piece is VEC floats -- and add the hit rows in
-// run order.  Neighbouring lanes read neighbouring pieces of one value row, so a value row is read as one contiguous
-// run of bytes, and the wave's output is one contiguous block.
+// all searches of the wave's rows proceed side by side; wave_sum_pieces then adds the hit rows in run order.
 template <int RL, int VEC>
 __global__ __launch_bounds__(kThreads) void rows_sum_wide_kernel(SumArgs a) {
   typedef typename Piece<VEC>::T P;
@@ -114,32 +152,10 @@ __global__ __launch_bounds__(kThreads) void rows_sum_wide_kernel(SumArgs a) {
       hit = find_in_run(a.grad_indexes, lo, end, a.indexes[i]);
     }
   }
-  const int pieces = a.dims / VEC;                  // per row
-  const int64_t left = a.rows - row0;
-  const int here = int(left < RPW ? left : RPW);    // rows of this wave
-  const int units = here * pieces;
   const P* __restrict__ values = reinterpret_cast<const P*>(a.grad_values);
-  P* out = reinterpret_cast<P*>(a.out) + row0 * pieces;
-  for (int e0 = 0; e0 < units; e0 += GS_WAVE) {     // wave-uniform trip count: the cross-lane reads see every lane
-    const int e = e0 + lane;
-    const bool live = e < units;
-    const int slot = live ? e / pieces : 0;
-    const int c = e - slot * pieces;
-    P v[RL];
-    int at[RL];
-#pragma unroll
-    for (int r = 0; r < RL; ++r) {
-      at[r] = __shfl(hit, slot * RL + r);
-      if (!live) at[r] = -1;
-      v[r] = piece_zero(P());
-      if (at[r] >= 0) v[r] = values[int64_t(at[r]) * pieces + c];
-    }
-    P acc = piece_zero(P());
-#pragma unroll
-    for (int r = 0; r < RL; ++r)
-      if (at[r] >= 0) acc = piece_add(acc, v[r]);
-    if (live) out[e] = acc;
-  }
+  const int pieces = a.dims / VEC;
+  wave_sum_pieces<RL, VEC>(hit, lane, row0, a.rows, pieces, a.out,
+                           [&](int, int at) { return values + int64_t(at) * pieces; });
 }
 
 // Narrow rows (1 to 4 floats): a lane per row, its runs searched one after the other; V4: 16-byte accesses for D = 4.
@@ -192,6 +208,96 @@ void launch_wide_runs(const SumArgs& a, hipStream_t s) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---------------------------------------------------------------------------------------------------- views_sum_rows
+// The same sum with the searches replaced by table reads: view b has its value row of Gaussian i at slot_of_b[i].  For
+// ascending `indexes` the slot reads of a view are near-sequential.  The tables travel in the kernel arguments.
+struct ViewsArgs {
+  int64_t rows;
+  const int64_t* indexes;
+  int views;
+  int dims;
+  float* out;
+  const int32_t* slot_of[GS_VIEWS_MAX];
+  const float* values[GS_VIEWS_MAX];
+  int32_t count[GS_VIEWS_MAX];
+  int32_t stride[GS_VIEWS_MAX];  // floats; of VEC-float pieces in the VEC = 4 kernels
+};
+
+// Wide rows: RL lanes per row (RL >= views) read one view's slot each; a slot outside [0, count) is no hit.
+template <int RL, int VEC>
+__global__ __launch_bounds__(kThreads) void views_sum_wide_kernel(ViewsArgs a) {
+  typedef typename Piece<VEC>::T P;
+  constexpr int RPW = GS_WAVE / RL;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t(blockIdx.x) * kThreads + threadIdx.x) >> 6;
+  const int64_t row0 = wave * RPW;
+  if (row0 >= a.rows) return;  // the whole wave
+  int hit = -1;
+  {
+    const int64_t i = row0 + lane / RL;
+    const int r = lane % RL;
+    if (i < a.rows && r < a.views) {
+      const int32_t* table = a.slot_of[0];
+      int count = a.count[0];
+#pragma unroll
+      for (int k = 1; k < RL; ++k)  // a select per view: the tables stay in scalar registers
+        if (r == k) { table = a.slot_of[k]; count = a.count[k]; }
+      const int64_t want = a.indexes[i];
+      const int slot = want >= 0 ? table[want] : -1;
+      hit = (slot >= 0 && slot < count) ? slot : -1;
+    }
+  }
+  wave_sum_pieces<RL, VEC>(hit, lane, row0, a.rows, a.dims / VEC, a.out, [&](int r, int at) {
+    return reinterpret_cast<const P*>(a.values[r]) + int64_t(at) * a.stride[r];
+  });
+}
+
+// Narrow rows (1 to 4 floats): a lane per row, the views one after the other; V4: 16-byte accesses for D = 4.
+template <int D, bool V4>
+__global__ __launch_bounds__(kThreads) void views_sum_narrow_kernel(ViewsArgs a) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= a.rows) return;
+  const int64_t want = a.indexes[i];
+  float acc[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) acc[j] = 0.0f;
+#pragma unroll
+  for (int b = 0; b < GS_VIEWS_MAX; ++b) {
+    if (b >= a.views) break;
+    const int slot = want >= 0 ? a.slot_of[b][want] : -1;
+    if (slot < 0 || slot >= a.count[b]) continue;
+    if (V4) {
+      const float4 v = reinterpret_cast<const float4*>(a.values[b])[int64_t(slot) * a.stride[b]];
+      acc[0] += v.x; acc[1 % D] += v.y; acc[2 % D] += v.z; acc[3 % D] += v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < D; ++j) acc[j] += a.values[b][int64_t(slot) * a.stride[b] + j];
+    }
+  }
+  if (V4) {
+    reinterpret_cast<float4*>(a.out)[i] = make_float4(acc[0], acc[1 % D], acc[2 % D], acc[3 % D]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < D; ++j) a.out[i * D + j] = acc[j];
+  }
+}
+
+template <int RL, int VEC>
+void launch_views_wide(const ViewsArgs& a, hipStream_t s) {
+  const int64_t waves = gs_div_up(a.rows, GS_WAVE / RL);
+  hipLaunchKernelGGL((views_sum_wide_kernel<RL, VEC>), dim3(unsigned(gs_div_up(waves, kThreads / GS_WAVE))),
+                     dim3(kThreads), 0, s, a);
+}
+
+template <int VEC>
+void launch_views_wide_lanes(const ViewsArgs& a, hipStream_t s) {
+  if (a.views <= 1) launch_views_wide<1, VEC>(a, s);
+  else if (a.views <= 2) launch_views_wide<2, VEC>(a, s);
+  else if (a.views <= 4) launch_views_wide<4, VEC>(a, s);
+  else if (a.views <= 8) launch_views_wide<8, VEC>(a, s);
+  else launch_views_wide<16, VEC>(a, s);
+}
+
 // ---------------------------------------------------------------------------------------------------- union
 // The bitmap: one bit per row of [0, n), in 32-bit words; a thread of the count and emit passes owns 4 words (one
 // 16-byte read, 128 rows), a workgroup 1024 words (32768 rows).  scratch = the words, padded to whole workgroups, then
@@ -209,6 +315,40 @@ __global__ __launch_bounds__(kThreads) void union_mark_kernel(int64_t n, int64_t
   const int64_t r = rows[i];
   if (r < 0 || r >= n) return;
   atomicOr(&words[r >> 5], 1u << (r & 31));
+}
+
+// The bitmap of the union of several views, from their slot_of tables (n int32 each, negative = not in the view) and
+// without atomics: a lane reads VEC consecutive entries of every table (VEC = 4: one 16-byte read), the 32 / VEC
+// neighbouring lanes of a word put their bits together by cross-lane ORs and the first of them stores the word.  One
+// streaming pass over the tables; every word of the padded bitmap is written, zeros behind row n: nothing to clear.
+struct ViewTables {
+  int views;
+  const int32_t* slot_of[GS_VIEWS_MAX];
+};
+
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void views_words_kernel(int64_t n, ViewTables t, unsigned* words) {
+  constexpr int LPW = 32 / VEC;  // lanes per word
+  const int64_t g = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  const int64_t row = g * VEC;
+  unsigned bits = 0;
+#pragma unroll
+  for (int b = 0; b < GS_VIEWS_MAX; ++b) {
+    if (b >= t.views) break;
+    if (VEC == 4 && row + 3 < n) {
+      const int4 s = *reinterpret_cast<const int4*>(t.slot_of[b] + row);
+      bits |= unsigned(s.x >= 0) | unsigned(s.y >= 0) << 1 | unsigned(s.z >= 0) << 2 | unsigned(s.w >= 0) << 3;
+    } else {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        if (row + j < n) bits |= unsigned(t.slot_of[b][row + j] >= 0) << j;
+    }
+  }
+  const int lane = threadIdx.x & 63;
+  unsigned word = bits << (VEC * (lane % LPW));
+#pragma unroll
+  for (int off = 1; off < LPW; off <<= 1) word |= __shfl_xor(word, off);  // no lane has left: the grid is whole words
+  if (lane % LPW == 0) words[g / LPW] = word;
 }
 
 __device__ __forceinline__ int popcount4(const uint4& w) {
@@ -271,6 +411,16 @@ __global__ __launch_bounds__(kThreads) void union_emit_kernel(const uint4* words
       bits &= bits - 1;
     }
   }
+}
+
+// the bitmap in `words` (the front of the scratch of n rows) to the ascending list: word-popcount scan, emit
+void union_scan_emit(int64_t n, unsigned* words, int64_t* union_rows, int32_t* union_count, hipStream_t s) {
+  const int64_t blocks = union_blocks(n);
+  int* block_counts = reinterpret_cast<int*>(reinterpret_cast<char*>(words) + union_word_bytes(n));
+  hipLaunchKernelGGL(union_count_kernel, dim3(unsigned(blocks)), dim3(kThreads), 0, s,
+                     reinterpret_cast<const uint4*>(words), block_counts);
+  hipLaunchKernelGGL(union_emit_kernel, dim3(unsigned(blocks)), dim3(kThreads), 0, s,
+                     reinterpret_cast<const uint4*>(words), block_counts, union_rows, union_count);
 }
 
 }  // namespace
@@ -336,16 +486,83 @@ extern "C" int gs_rows_union(int64_t n, int64_t count, const int64_t* rows, int6
              (long long)gs_rows_union_scratch_bytes(n));
   GS_REQUIRE(aligned16(scratch), GS_ERR_INVALID_ARGUMENT, "gs_rows_union: scratch is not 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t blocks = union_blocks(n);
   unsigned* words = static_cast<unsigned*>(scratch);
-  int* block_counts = reinterpret_cast<int*>(static_cast<char*>(scratch) + union_word_bytes(n));
   if (int rc = gs_memset_async(words, size_t(union_word_bytes(n)), s, "gs_rows_union: clearing the bitmap failed")) return rc;
   hipLaunchKernelGGL(union_mark_kernel, dim3(unsigned(gs_div_up(count, kThreads))), dim3(kThreads), 0, s, n, count,
                      rows, words);
-  hipLaunchKernelGGL(union_count_kernel, dim3(unsigned(blocks)), dim3(kThreads), 0, s,
-                     reinterpret_cast<const uint4*>(words), block_counts);
-  hipLaunchKernelGGL(union_emit_kernel, dim3(unsigned(blocks)), dim3(kThreads), 0, s,
-                     reinterpret_cast<const uint4*>(words), block_counts, union_rows, union_count);
+  union_scan_emit(n, words, union_rows, union_count, s);
   GS_CHECK_LAUNCH("gs_rows_union");
+  return GS_OK;
+}
+
+extern "C" int64_t gs_views_union_scratch_bytes(int64_t n) { return gs_rows_union_scratch_bytes(n); }
+
+extern "C" int gs_views_union(int64_t n, int32_t views, const int32_t* const* slot_of_host, int64_t* union_rows,
+                              int32_t* union_count, void* scratch, int64_t scratch_bytes, void* stream) {
+  GS_REQUIRE(n >= 0 && n < (int64_t(1) << 31), GS_ERR_INVALID_ARGUMENT, "gs_views_union: %lld rows", (long long)n);
+  GS_REQUIRE(views >= 0 && views <= GS_VIEWS_MAX, GS_ERR_INVALID_ARGUMENT, "gs_views_union: views %d not in [0,%d]",
+             views, GS_VIEWS_MAX);
+  if (n == 0 || views == 0) return GS_OK;
+  GS_REQUIRE(slot_of_host && union_rows && union_count, GS_ERR_INVALID_ARGUMENT, "gs_views_union: NULL buffer");
+  ViewTables t{};
+  t.views = views;
+  bool v4 = true;
+  for (int b = 0; b < views; ++b) {
+    GS_REQUIRE(slot_of_host[b], GS_ERR_INVALID_ARGUMENT, "gs_views_union: NULL buffer (slot_of of view %d)", b);
+    t.slot_of[b] = slot_of_host[b];
+    v4 = v4 && aligned16(slot_of_host[b]);
+  }
+  GS_REQUIRE(scratch && scratch_bytes >= gs_views_union_scratch_bytes(n), GS_ERR_SCRATCH_TOO_SMALL,
+             "gs_views_union: scratch of %lld bytes, %lld needed", (long long)scratch_bytes,
+             (long long)gs_views_union_scratch_bytes(n));
+  GS_REQUIRE(aligned16(scratch), GS_ERR_INVALID_ARGUMENT, "gs_views_union: scratch is not 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned* words = static_cast<unsigned*>(scratch);
+  const int64_t word_blocks = union_blocks(n) * kWordsPerThread;  // workgroups of one lane per word
+  if (v4) hipLaunchKernelGGL(views_words_kernel<4>, dim3(unsigned(word_blocks * 8)), dim3(kThreads), 0, s, n, t, words);
+  else hipLaunchKernelGGL(views_words_kernel<1>, dim3(unsigned(word_blocks * 32)), dim3(kThreads), 0, s, n, t, words);
+  union_scan_emit(n, words, union_rows, union_count, s);
+  GS_CHECK_LAUNCH("gs_views_union");
+  return GS_OK;
+}
+
+extern "C" int gs_views_sum_rows(int64_t rows, const int64_t* indexes, int32_t views, const GsViewRows* view_rows_host,
+                                 int32_t dims, float* out, void* stream) {
+  GS_REQUIRE(dims >= 1, GS_ERR_INVALID_ARGUMENT, "gs_views_sum_rows: dims %d", dims);
+  GS_REQUIRE(dims <= (1 << 20), GS_ERR_UNSUPPORTED, "gs_views_sum_rows: rows of %d floats (at most %d)", dims, 1 << 20);
+  GS_REQUIRE(rows >= 0 && rows < (int64_t(1) << 31), GS_ERR_INVALID_ARGUMENT, "gs_views_sum_rows: %lld rows",
+             (long long)rows);
+  GS_REQUIRE(views >= 0 && views <= GS_VIEWS_MAX, GS_ERR_INVALID_ARGUMENT, "gs_views_sum_rows: views %d not in [0,%d]",
+             views, GS_VIEWS_MAX);
+  if (rows == 0) return GS_OK;
+  GS_REQUIRE(indexes && out && (views == 0 || view_rows_host), GS_ERR_INVALID_ARGUMENT,
+             "gs_views_sum_rows: NULL buffer");
+  ViewsArgs a{};
+  a.rows = rows; a.indexes = indexes; a.dims = dims; a.out = out;
+  bool v4 = dims % 4 == 0 && aligned16(out);
+  for (int b = 0; b < views; ++b) {  // a view without value rows adds nothing: it is left out, the order of the rest kept
+    const GsViewRows& v = view_rows_host[b];
+    GS_REQUIRE(v.count >= 0 && v.count < (int64_t(1) << 31), GS_ERR_INVALID_ARGUMENT,
+               "gs_views_sum_rows: view %d has %lld value rows", b, (long long)v.count);
+    if (v.count == 0) continue;
+    GS_REQUIRE(v.slot_of && v.values, GS_ERR_INVALID_ARGUMENT, "gs_views_sum_rows: NULL buffer (view %d)", b);
+    GS_REQUIRE(v.stride >= dims, GS_ERR_INVALID_ARGUMENT, "gs_views_sum_rows: view %d has a stride of %d for %d floats",
+               b, v.stride, dims);
+    const int k = a.views++;
+    a.slot_of[k] = v.slot_of; a.values[k] = v.values; a.count[k] = int32_t(v.count); a.stride[k] = v.stride;
+    v4 = v4 && v.stride % 4 == 0 && aligned16(v.values);
+  }
+  if (v4)
+    for (int k = 0; k < a.views; ++k) a.stride[k] /= 4;  // in 16-byte pieces
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 lanes(unsigned(gs_div_up(rows, kThreads)));
+  if (dims == 1) hipLaunchKernelGGL((views_sum_narrow_kernel<1, false>), lanes, dim3(kThreads), 0, s, a);
+  else if (dims == 2) hipLaunchKernelGGL((views_sum_narrow_kernel<2, false>), lanes, dim3(kThreads), 0, s, a);
+  else if (dims == 3) hipLaunchKernelGGL((views_sum_narrow_kernel<3, false>), lanes, dim3(kThreads), 0, s, a);
+  else if (dims == 4 && v4) hipLaunchKernelGGL((views_sum_narrow_kernel<4, true>), lanes, dim3(kThreads), 0, s, a);
+  else if (dims == 4) hipLaunchKernelGGL((views_sum_narrow_kernel<4, false>), lanes, dim3(kThreads), 0, s, a);
+  else if (v4) launch_views_wide_lanes<4>(a, s);
+  else launch_views_wide_lanes<1>(a, s);
+  GS_CHECK_LAUNCH("gs_views_sum_rows");
   return GS_OK;
 }

@@ -342,11 +342,24 @@ def _exchange(m, rows, feats):
 
 
 def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha=None):
+    """the seven input gradients of the frame; with sparse_grad the five of the Gaussians as sparse tensors over
+    points_in_view (_backward_rows, _as_sparse)"""
+    saved = ctx.saved_tensors  # read before the backward: a second pass (retain_graph) clears rows of the workspace
+    outs, d_T, d_proj = _backward_rows(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha)
+    if ctx.meta["sparse_grad"]:
+        m = ctx.meta
+        outs = _as_sparse(outs, saved[:5], saved[7], m["frame"][1], m["V"])
+    return (*outs, d_T, d_proj)
+
+
+def _backward_rows(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha=None):
     """the frame's backward on the workspace of its gs_frame_fwd: one gs_frame_bwd call when the forward prepared it,
     otherwise three -- rasterizer, colour adjoint, projection adjoint -- with a sharded frame's exchange of its partial
-    gradients after the first; returns the seven input gradients.  g_alpha: the gradient of image_weight of a frame
-    rendered with differentiable_weight (the rasterizer's backward takes it into every pixel's initial R; the divisor
-    of depth / depth_var stays a constant)"""
+    gradients after the first; returns (the five Gaussian gradients, dL/dT, dL/dprojection), the five row-compact with
+    sparse_grad: (max(V, 1), ...) pieces of one allocation, row i the gradient of Gaussian points_in_view[i].  g_alpha:
+    the gradient of image_weight of a frame rendered with differentiable_weight (the rasterizer's backward takes it into
+    every pixel's initial R; the divisor of depth / depth_var stays a constant).  `ctx`: anything that carries the
+    frame's meta, camera_grads, heur, holder and saved_tensors (_FrameRender's context, a _View of _ViewsRender)"""
     saved = ctx.saved_tensors
     inputs, ws = saved[:7], saved[7]
     position, log_scaling, rotation, alpha_logit, feature, T, proj = inputs
@@ -428,9 +441,7 @@ def _backward(ctx, g_image, g_points, g_depth, g_img_depth, g_img_var, g_alpha=N
             wait.wait()
         _publish(ctx, rows if pp is None else pp, V)  # before the PROJECT call adds the attached gradient
         call(range(nv.GS_BWD_PROJECT, nv.GS_BWD_STAGES), splats=pp)
-    if compact:
-        outs = _as_sparse(outs, params, ws, L, V)
-    return (*outs, _add_centre_grad(d_T, d_centre, T), d_proj)
+    return outs, _add_centre_grad(d_T, d_centre, T), d_proj
 
 
 def _as_sparse(rows, params, ws, L, V):
@@ -493,6 +504,185 @@ class _OwnedRender(torch.autograd.Function):
         return _FrameRender.backward(ctx, *grads)[:5] + (None,) * (len(ctx.needs_input_grad) - 5)
 
 
+class _View:
+    """What _forward leaves on an autograd context and _backward_rows reads there, for ONE view of _ViewsRender: the
+    views' tensors are all saved on that node's own context, which hands a view its eight before the view's backward."""
+
+    def __init__(self):
+        self.saved_tensors = ()
+        self.non_differentiable = []
+
+    def set_materialize_grads(self, value):
+        pass  # the node's own context
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+    def mark_non_differentiable(self, *tensors):
+        self.non_differentiable.extend(tensors)
+
+
+_VIEW_OUTPUTS = 10   # of _forward, per view
+_VIEWS_CAMERAS = 7   # position of the first camera matrix among the arguments of _ViewsRender.forward behind ctx
+
+
+def _view_tables(entries):
+    """the host table of gs_views_sum_rows from (workspace, layout, values, count, stride) per view.  The caller keeps
+    the tensors referenced until the launch has been issued."""
+    table = (nv.GsViewRows * max(len(entries), 1))()
+    for k, (ws, L, values, count, stride) in enumerate(entries):
+        table[k] = nv.GsViewRows(ws.data_ptr() + L.slot_of, values.data_ptr() if count > 0 else None, count, stride)
+    return table
+
+
+class _ViewsRender(torch.autograd.Function):
+    """B frames of the same Gaussians as ONE autograd node (renderer.render_views).  Forward: one gs_frame_fwd per view
+    as in _FrameRender, then the union of the views' visible rows from the workspaces' slot_of tables (gs_views_union)
+    and, with compute_visibility, the visibility summed over the views (gs_views_sum_rows); one host read for the size
+    of the union.  Backward: the frame backward of every view that received a gradient, into its own row-compact
+    pieces, then one gs_views_sum_rows per parameter over all those views at once, on the union's rows: the sum in
+    view order, no sort, no search, nothing through autograd's sparse `+`.
+    Memory: the B workspaces stay alive until the backward, and during it the compact gradient rows of all views
+    (sum of V_b rows) and the merged ones (U rows) exist side by side.
+    forward(position, log_scaling, rotation, alpha_logit, feature, spec, background, T_0, projection_0, T_1, ...);
+    returns the ten outputs of _forward for every view, then the union (U) int64 and its summed visibility."""
+
+    @staticmethod
+    @nv.on_tensor_device
+    def forward(ctx, position, log_scaling, rotation, alpha_logit, feature, spec, background, *cameras):
+        params = (position, log_scaling, rotation, alpha_logit, feature)
+        needs = ctx.needs_input_grad
+        lib, dev, n = nv.lib(), position.device, position.shape[0]
+        views, outs, saved = [], [], []
+        for b, (image_size, depth_range, holder, key) in enumerate(spec["frames"]):
+            view = _View()
+            at = _VIEWS_CAMERAS + 2 * b
+            view_needs = (*needs[:5], needs[at], needs[at + 1])
+            colour = background if background is None or background.dim() == 1 else background[b]
+
+            def render(k_cap, tile_hint):
+                return _forward(view, view_needs, *params, cameras[2 * b], cameras[2 * b + 1], image_size, depth_range,
+                                spec["config"], spec["render_depth"], spec["use_depth16"], spec["render_median"], None,
+                                None, holder, "dense", "replicated", None, True, key, k_cap, tile_hint, colour,
+                                spec["differentiable_weight"])
+            outs.extend(_at_capacity(render, key))
+            saved.extend(view.saved_tensors[5:])  # the contiguous camera matrices, the workspace
+            views.append(view)
+        frames = [(view.saved_tensors[7], view.meta["frame"][1], view.meta["V"]) for view in views]
+        total = sum(V for _, _, V in frames)
+        union = torch.empty((min(n, total),), dtype=torch.int64, device=dev)
+        U = 0
+        if total > 0:
+            need = lib.gs_views_union_scratch_bytes(n)
+            scratch = nv.scratch(need, dev)
+            count = torch.empty((1,), dtype=torch.int32, device=dev)
+            tables = (ctypes.c_void_p * len(frames))(*[ws.data_ptr() + L.slot_of for ws, L, _ in frames])
+            nv.check(lib.gs_views_union(n, len(frames), tables, nv.ptr(union), nv.ptr(count), nv.ptr(scratch), need,
+                                        nv.stream()), "gs_views_union")
+            U = int(count.item())  # the one host read of the batch
+        union = union[:U]
+        visibility = _empty(dev, (0,))
+        if spec["config"].compute_visibility:
+            visibility = torch.empty((U,), dtype=torch.float32, device=dev)
+            if U > 0:
+                seen = [(ws, L, _carve(ws.view(torch.float32), L.visibility, (V,)), V, 1) for ws, L, V in frames]
+                nv.check(lib.gs_views_sum_rows(U, nv.ptr(union), len(seen), _view_tables(seen), 1, nv.ptr(visibility),
+                                               nv.stream()), "gs_views_sum_rows")
+        for view in views:
+            view.saved_tensors = ()
+        ctx.views, ctx.spec = views, spec
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*params, union, *saved)
+        ctx.mark_non_differentiable(*(t for view in views for t in view.non_differentiable), union, visibility)
+        return (*outs, union, visibility)
+
+    @staticmethod
+    @nv.on_tensor_device
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        params, union = saved[:5], saved[5]
+        views, needs = ctx.views, ctx.needs_input_grad
+        dev, U = union.device, union.shape[0]
+        need_background = needs[_VIEWS_CAMERAS - 1]
+        camera_grads, background_grads = [None] * (2 * len(views)), [None] * len(views)
+        done = []  # (workspace, layout, the five compact pieces, V) of the views that received a gradient, in view order
+        for b, view in enumerate(views):
+            g_image, g_alpha, g_points, g_depth, _, _, _, g_img_depth, g_img_var, _ = \
+                grads[_VIEW_OUTPUTS * b:_VIEW_OUTPUTS * (b + 1)]
+            if all(g is None for g in (g_image, g_alpha, g_points, g_depth, g_img_depth, g_img_var)):
+                continue  # left out of the loss
+            view.saved_tensors = (*params, *saved[6 + 3 * b:9 + 3 * b])
+            rows, camera_grads[2 * b], camera_grads[2 * b + 1] = _backward_rows(view, g_image, g_points, g_depth,
+                                                                                g_img_depth, g_img_var, g_alpha)
+            if need_background:
+                background_grads[b] = _background_grad(view, g_image)
+            done.append((view.saved_tensors[7], view.meta["frame"][1], rows, view.meta["V"]))
+            view.saved_tensors = ()
+        # the merged rows: one allocation, the pieces on 256-byte boundaries like the frames' own
+        widths = [t.numel() // t.shape[0] for t in params]
+        starts, at = [], 0
+        for width in widths:
+            starts.append(at)
+            at += -(-U * width // 64) * 64
+        flat = torch.empty((at,), dtype=torch.float32, device=dev)
+        merged = [flat.as_strided((U, *t.shape[1:]), t.stride(), start) for t, start in zip(params, starts)]
+        if U > 0:
+            lib = nv.lib()
+            for k, width in enumerate(widths):
+                entries = [(ws, L, rows[k], V, width) for ws, L, rows, V in done]
+                nv.check(lib.gs_views_sum_rows(U, nv.ptr(union), len(entries), _view_tables(entries), width,
+                                               nv.ptr(merged[k]), nv.stream()), "gs_views_sum_rows")
+        if ctx.spec["sparse_grad"]:
+            idx = union.clone().view(1, U)  # fresh and shared by the five: .grad keeps neither a workspace nor the node
+            _register_sparse_indexes(idx)
+            d_params = [torch.sparse_coo_tensor(idx, r, t.shape, is_coalesced=True) for r, t in zip(merged, params)]
+        else:
+            d_params = [torch.zeros_like(t).index_copy_(0, union, r) for r, t in zip(merged, params)]
+        d_background = None
+        if need_background:
+            C = params[4].shape[1]
+            parts = [torch.zeros((C,), dtype=torch.float32, device=dev) if g is None else g for g in background_grads]
+            d_background = torch.stack(parts)
+            if ctx.spec["background_dim"] == 1:
+                d_background = d_background.sum(0)
+        return (*d_params, None, d_background, *camera_grads)
+
+
+def render_views_fused(gaussians, cameras, config: RasterConfig, render_depth: bool, use_depth16: bool,
+                       render_median_depth: bool, sparse_grad: bool, background, differentiable_weight: bool):
+    """(the views' Renderings, the union of their points_in_view, its summed visibility or None): see
+    renderer.render_views and _ViewsRender"""
+    from .renderer import Rendering
+    params = (gaussians.position.contiguous(), gaussians.log_scaling.contiguous(), gaussians.rotation.contiguous(),
+              gaussians.alpha_logit.contiguous(), gaussians.feature.contiguous())
+    n = params[0].shape[0]
+    frames, matrices = [], []
+    for cam in cameras:
+        size = cam.image_size
+        key = (n, int(size[0]), int(size[1]), None, config.tile_size, bool(use_depth16))
+        frames.append((size, cam.depth_range, {}, key))
+        matrices += [cam.T_camera_world, cam.projection]
+    spec = dict(frames=frames, config=config, render_depth=render_depth, use_depth16=use_depth16,
+                render_median=render_median_depth, differentiable_weight=bool(differentiable_weight),
+                sparse_grad=bool(sparse_grad), background_dim=0 if background is None else background.dim())
+    outs = _ViewsRender.apply(*params, spec, background, *matrices)
+    renderings = []
+    for b, cam in enumerate(cameras):
+        image, alpha, g2d, depths, indexes, vis, heur, img_depth, img_var, median = \
+            outs[_VIEW_OUTPUTS * b:_VIEW_OUTPUTS * (b + 1)]
+        frames[b][2]["gaussians2d"] = weakref.ref(g2d)
+        indexes._gs_unique = True
+        renderings.append(Rendering(
+            image=image, image_weight=alpha, depth=img_depth if render_depth else None,
+            depth_var=img_var if render_depth else None, median_depth=median if render_median_depth else None,
+            camera=cam, config=config, point_visibility=vis if config.compute_visibility else None,
+            point_heuristic=heur if config.compute_point_heuristic else None, points_in_view=indexes,
+            point_depth=depths, gaussians2d=g2d))
+    union, visibility = outs[-2], outs[-1]
+    union._gs_unique = True
+    return renderings, union, visibility if config.compute_visibility else None
+
+
 def fused_supported(gaussians, camera_params, use_sh: bool, render_median_depth: bool) -> bool:
     """The fused node covers SH colours (N, C <= 8, D) and plain features (N, C <= 30), with or without the depth
     and median-depth images, camera gradients included.  What is left -- an empty scene, wider features -- runs the
@@ -511,6 +701,25 @@ def _capacity(hint):
     k_cap = -(-(int(hint[0] * 1.25) + 4096) // 65536) * 65536
     tile_hint = next((c for c in (256, 512, 1024, 2048) if hint[1] <= c), 4096)
     return k_cap, tile_hint
+
+
+def _at_capacity(render, key):
+    """render(k_cap, tile_hint) at the capacity class of the shape `key` (seen for the first time: the smallest class); a
+    frame with more overlaps than that is run once more, sized for the K its first attempt recorded"""
+    outs = None
+    try:
+        outs = render(*_capacity(_K_HINT.get(key, (0, 0))))
+    except _Overflow:  # more overlaps than the capacity: K is recorded now
+        pass
+    if outs is None:
+        # run again outside the except block, whose traceback still holds the failed attempt's workspace; the mapper
+        # is deterministic, so the same frame at a capacity of at least its K cannot overflow again
+        try:
+            outs = render(*_capacity(_K_HINT[key]))
+        except _Overflow:
+            raise RuntimeError(f"render_gaussians: the re-run of an overflowing frame overflowed again (hint "
+                               f"{_K_HINT[key]})") from None
+    return outs
 
 
 def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: bool, use_depth16: bool,
@@ -546,20 +755,7 @@ def render_fused(gaussians, camera_params, config: RasterConfig, render_depth: b
     else:
         def render(*sizes):
             return _FrameRender.apply(*args, key, *sizes, background, bool(differentiable_weight))
-    # a shape seen for the first time gets the smallest capacity class
-    outs = None
-    try:
-        outs = render(*_capacity(_K_HINT.get(key, (0, 0))))
-    except _Overflow:  # more overlaps than the capacity: K is recorded now
-        pass
-    if outs is None:
-        # run again outside the except block, whose traceback still holds the failed attempt's workspace; the mapper
-        # is deterministic, so the same frame at a capacity of at least its K cannot overflow again
-        try:
-            outs = render(*_capacity(_K_HINT[key]))
-        except _Overflow:
-            raise RuntimeError(f"render_gaussians: the re-run of an overflowing frame overflowed again (hint "
-                               f"{_K_HINT[key]})") from None
+    outs = _at_capacity(render, key)
     image, alpha, g2d, depths, indexes, vis, heur, img_depth, img_var, median = outs
     holder["gaussians2d"] = weakref.ref(g2d)
     indexes._gs_unique = True

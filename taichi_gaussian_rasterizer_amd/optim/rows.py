@@ -107,7 +107,11 @@ def visible_union(renderings, *, num_points: Optional[int] = None):
     """(indexes, visibility) for `VisibilityAware*.step` after one backward per rendering: the union of the frames'
     `points_in_view` and the visibility summed over the views (a caller who wants the mean divides); visibility is None
     when the frames carry none.  `num_points`: the number of Gaussians; left out, it is taken from the largest row any
-    frame lists, which costs a host read of its own."""
+    frame lists, which costs a host read of its own.  A `RenderedViews` (render_views) carries the pair already: it is
+    returned as stored, without a launch."""
+    from ..renderer import RenderedViews
+    if isinstance(renderings, RenderedViews):
+        return renderings.points_in_view, renderings.point_visibility
     renderings = list(renderings)
     lists = [r.points_in_view for r in renderings]
     values = [r.point_visibility for r in renderings]

@@ -9,6 +9,7 @@ renderer.py:28-131: same field and property names).
 from __future__ import annotations
 
 import dataclasses
+from collections.abc import Sequence
 from functools import cached_property
 from numbers import Integral
 from typing import Optional, Tuple
@@ -156,6 +157,16 @@ def _refuse_float64(gaussians, camera_params) -> None:
                         "evaluate_sh_at and rasterize_with_tiles, for gradcheck)")
 
 
+def _refuse_unfused(gaussians, use_sh: bool, what: str) -> None:
+    """a frame the fused node does not cover where only that node will do; tensors that are not float32 on the device
+    are refused first, with the error every operator gives them"""
+    feature = gaussians.feature
+    nv.require_device(*gaussians.shape_tensors(), feature, what=what)
+    raise NotImplementedError(
+        f"{what}: only the fused frame produces sparse gradients (SH colours, or plain "
+        f"features up to 30 channels); got features of shape {tuple(feature.shape)} with use_sh={use_sh}")
+
+
 def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config: RasterConfig = RasterConfig(),
                      use_sh: bool = False, render_depth: bool = False, use_depth16: bool = False,
                      render_median_depth: bool = False, background: Optional[torch.Tensor] = None,
@@ -197,14 +208,9 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
         return render_fused(gaussians, camera_params, config, render_depth, use_depth16,
                             render_median_depth=render_median_depth, sparse_grad=sparse_grad,
                             background=background, differentiable_weight=differentiable_weight)
-    feature = gaussians.feature
     if sparse_grad and gaussians.position.shape[0] > 0:
-        # an empty scene has no rows to be sparse over and renders as it always did; tensors that are not float32 on
-        # the device are refused here with the error every operator gives them
-        nv.require_device(*gaussians.shape_tensors(), feature, what="render_gaussians(sparse_grad=True)")
-        raise NotImplementedError(
-            f"render_gaussians(sparse_grad=True): only the fused frame produces sparse gradients (SH colours, or plain "
-            f"features up to 30 channels); got features of shape {tuple(feature.shape)} with use_sh={use_sh}")
+        # an empty scene has no rows to be sparse over and renders as it always did
+        _refuse_unfused(gaussians, use_sh, "render_gaussians(sparse_grad=True)")
 
     splats, depths, visible, sort_depths = project_with_ndc(
         *gaussians.shape_tensors(), camera_params.T_camera_world, camera_params.projection,
@@ -219,6 +225,93 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
                             use_depth16=use_depth16, render_median_depth=render_median_depth,
                             ndc_depths=sort_depths, background=background,
                             differentiable_weight=differentiable_weight)
+
+
+class RenderedViews(Sequence):
+    """What `render_views` produced: a sequence of the B views' `Rendering`s (len, indexing, iteration; `.renderings`
+    is the tuple), plus what the batch has as a whole -- `points_in_view`, the ascending distinct union of the views'
+    `points_in_view` (the rows the merged gradient lists), and `point_visibility`, the views' visibility summed in view
+    order on those rows (None without config.compute_visibility)."""
+
+    def __init__(self, renderings, points_in_view: torch.Tensor, point_visibility: Optional[torch.Tensor]):
+        self.renderings = tuple(renderings)
+        self.points_in_view = points_in_view
+        self.point_visibility = point_visibility
+
+    def __len__(self) -> int:
+        return len(self.renderings)
+
+    def __getitem__(self, index):
+        return self.renderings[index]
+
+    @property
+    def visible(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(indexes, visibility) of the batch, as `VisibilityAware*.step(*views.visible)` takes them; unlike
+        `Rendering.visible` every listed row is kept, as `optim.visible_union` keeps them"""
+        assert self.point_visibility is not None, _NEED_VISIBILITY
+        return self.points_in_view, self.point_visibility
+
+    @property
+    def num_points(self) -> int:
+        return int(self.points_in_view.shape[0])
+
+
+def render_views(gaussians: Gaussians3D, cameras, config: RasterConfig = RasterConfig(), use_sh: bool = False,
+                 render_depth: bool = False, use_depth16: bool = False, render_median_depth: bool = False,
+                 background: Optional[torch.Tensor] = None, differentiable_weight: bool = False,
+                 sparse_grad: bool = True) -> RenderedViews:
+    """Render a batch of views of the same Gaussians as ONE autograd node (not a call of the reference).  `cameras`: 1 to
+    GS_VIEWS_MAX (16) CameraParams, which may differ in image size.  Every `Rendering` of the result has the fields and
+    the values `render_gaussians` gives for that camera; the losses of the views are summed (or given to
+    torch.autograd.backward together) and ONE backward leaves one gradient per parameter: the views' row-compact
+    gradients merged on the device in view order (gs_views_sum_rows), over the union of the views' visible rows
+    (`RenderedViews.points_in_view`) -- nothing goes through autograd's accumulation of sparse gradients, a sort or a
+    search.  A view no loss uses costs no backward; the gradient still lists the whole union.
+
+    sparse_grad=True (the default here): the five parameters receive `torch.sparse_coo` gradients, indices (1, U) = the
+    union, shared by the five, values (U, ...); the optimizers of `optim` step from them as from a single frame's own
+    (`opt.step(*views.visible)`).  sparse_grad=False: dense (N, ...) gradients, zero outside the union.  Camera gradients
+    are dense, one per view.  background: (C,) for all views or (B, C), one row per view; it may require grad.  Other
+    arguments as `render_gaussians`.
+
+    Only frames the fused node covers (SH colours, or plain features up to 30 channels), whatever sparse_grad is:
+    anything else raises NotImplementedError; float64 the TypeError of render_gaussians; an empty or too long `cameras`
+    ValueError.  An empty scene (N = 0) renders every view through render_gaussians and has an empty union.  Memory: the
+    B frames' workspaces live until the backward, which holds the compact gradient rows of all views (sum of V_b) at
+    once."""
+    cameras = list(cameras) if isinstance(cameras, (list, tuple)) else cameras
+    if not isinstance(cameras, list):
+        raise TypeError(f"cameras must be a list or tuple of CameraParams, got {type(cameras).__name__}")
+    if not 1 <= len(cameras) <= nv.GS_VIEWS_MAX:
+        raise ValueError(f"render_views: {len(cameras)} cameras; a batch has 1 to {nv.GS_VIEWS_MAX} views "
+                         "(GS_VIEWS_MAX)")
+    for b, cam in enumerate(cameras):
+        if not isinstance(cam, CameraParams):
+            raise TypeError(f"cameras[{b}] must be CameraParams, got {type(cam).__name__}")
+    _check_call(gaussians, cameras[0], config, dict(use_sh=use_sh, render_depth=render_depth, use_depth16=use_depth16,
+                                                    render_median_depth=render_median_depth, sparse_grad=sparse_grad,
+                                                    differentiable_weight=differentiable_weight))
+    for cam in cameras:
+        _refuse_float64(gaussians, cam)
+    feature = gaussians.feature
+    per_view = isinstance(background, torch.Tensor) and background.dim() == 2
+    if per_view:
+        assert background.shape[0] == len(cameras), \
+            f"render_views: a per-view background has one row per camera, got {tuple(background.shape)}"
+    if background is not None or differentiable_weight:
+        check_background(background[0] if per_view else background, differentiable_weight, config, feature,
+                         feature.shape[1] if feature.ndim >= 2 else 0, "render_views")
+    if gaussians.position.shape[0] == 0:
+        views = [render_gaussians(gaussians, cam, config, use_sh, render_depth, use_depth16, render_median_depth,
+                                  background=background[b] if per_view else background,
+                                  differentiable_weight=differentiable_weight) for b, cam in enumerate(cameras)]
+        nothing = views[0].points_in_view.new_empty((0,))
+        return RenderedViews(views, nothing, feature.new_empty((0,)) if config.compute_visibility else None)
+    from .fused import fused_supported, render_views_fused
+    if not fused_supported(gaussians, cameras[0], use_sh, render_median_depth):
+        _refuse_unfused(gaussians, use_sh, "render_views")
+    return RenderedViews(*render_views_fused(gaussians, cameras, config, render_depth, use_depth16,
+                                             render_median_depth, sparse_grad, background, differentiable_weight))
 
 
 def compute_depth_variance(depth_depthsq: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6):
