@@ -628,6 +628,73 @@ typedef struct GsViewRows {
 int gs_views_sum_rows(int64_t rows, const int64_t* indexes, int32_t views, const GsViewRows* view_rows_host,
                       int32_t dims, float* out, void* stream);
 
+/* ---------------------------------------------------------------------- densification --
+ * Changing the number of Gaussians (the reference does it in torch, optim/parameter_class.py __getitem__ and
+ * append_tensors): a plan says which source row every output row comes from, one launch moves every per-row table by
+ * it, a second one places the children of split rows, and a per-row table of statistics collects what the selection
+ * thresholds.  Selection itself (top-k, thresholds) is the caller's. */
+#define GS_DENSIFY_CHILDREN_MAX 8
+#define GS_MOVE_COLUMNS_MAX 32
+#define GS_DENSIFY_STATS 6
+
+/* The plan.  prune, split, clone: n bytes each, non-zero = set, NULL = none set.  Per row prune wins over split, split
+ * over clone: a pruned row disappears, a split row disappears and yields `children` (1 .. GS_DENSIFY_CHILDREN_MAX) new
+ * rows, a cloned row stays and yields one new row, every other row stays.  src_of (capacity int32) = the source row
+ * of every output row, in this order, which callers may rely on:
+ *   the kept rows ascending (the rows neither pruned nor split: the order of a boolean index),
+ *   then the clones, ascending by parent,
+ *   then the children, parent-major: the `children` rows of a parent are adjacent, parents ascend.
+ * counts (4 int32 on the device) = kept, clones, split parents, rows = kept + clones + children * split parents; they
+ * are right also when rows > capacity: entries at or behind `capacity` are not written.  No atomics: the same masks
+ * give the same plan.  n * max(2, children) < 2^31.  scratch: gs_densify_plan_scratch_bytes(n), 16-byte aligned.
+ * n == 0: nothing is written. */
+int64_t gs_densify_plan_scratch_bytes(int64_t n);
+int gs_densify_plan(int64_t n, const uint8_t* prune, const uint8_t* split, const uint8_t* clone, int32_t children,
+                    int64_t capacity, int32_t* src_of, int32_t* counts, void* scratch, int64_t scratch_bytes,
+                    void* stream);
+
+/* one column of a table: rows of row_bytes contiguous bytes (a positive multiple of 4; src and dst 4-byte aligned) */
+typedef struct GsMoveColumn {
+  const void* src;
+  void* dst;        /* `rows` rows; must not overlap src */
+  int32_t row_bytes;
+  int64_t copy_rows; /* 0 .. rows: dst rows from here on are zero-filled (fresh optimizer state) */
+} GsMoveColumn;
+
+/* For every column and every output row j < rows: dst[j] = src[src_of[j]] if j < copy_rows, else zero bytes.  One
+ * launch for all columns; columns_host: a HOST array of `columns` (0 .. GS_MOVE_COLUMNS_MAX) entries, passed to the
+ * kernel by value.  Rows move as bytes (NaN payloads, -0.0 and denormals survive), with 16-byte accesses in a column
+ * whose row_bytes, src and dst are all multiples of 16 and 4-byte accesses otherwise.  src_of[j] must be a row of src
+ * (not checked).  rows < 2^31, and a column has fewer than 2^32 - 2^19 access units (rows * row_bytes / 16, or / 4),
+ * GS_ERR_UNSUPPORTED otherwise.  rows == 0 or columns == 0: returns 0. */
+int gs_table_move_rows(int64_t rows, const int32_t* src_of, int32_t columns, const GsMoveColumn* columns_host,
+                       void* stream);
+
+/* The children of split 3D Gaussians.  count = children * split parents rows; parent_of (count int32: the tail of the
+ * plan's src_of) indexes the SOURCE tables position (n,3), log_scaling (n,3), rotation (n,4, xyzw).  Child t gets
+ *   child_position[t]    = position[p] + R(rotation[p] / |rotation[p]|) (exp(log_scaling[p]) * noise[t])
+ *   child_log_scaling[t] = log_scaling[p] - (float)log_shrink          (one float32 subtraction)
+ * with p = parent_of[t]; noise (count,3) comes from the caller (the library has no random numbers: the result is a
+ * function of the arguments); zero noise leaves the parent's position bits.  child_position / child_log_scaling
+ * (count,3): the first child row of the destination tables.  Everything else of a child is its parent's and is already
+ * in place after gs_table_move_rows. */
+int gs_split3d_children(int64_t count, int32_t children, const int32_t* parent_of, const float* position,
+                        const float* log_scaling, const float* rotation, const float* noise, double log_shrink,
+                        float* child_position, float* child_log_scaling, void* stream);
+
+/* stats (n, GS_DENSIFY_STATS) float32, updated in place from one view's row-compact results (v rows; row t belongs to
+ * Gaussian points_in_view[t]; entries outside [0, n) are skipped):
+ *   0  += 1 where visibility[t] > 0 (every listed row when visibility is NULL)
+ *   1  += sqrt(gx^2 + gy^2), (gx, gy) = grad2d[t * grad2d_stride + 0 .. 2): the gradient of the projected mean
+ *   2  += heuristic[t][0] (prune cost)      3  += heuristic[t][1] (split score)
+ *   4  += visibility[t]
+ *   5   = max(itself, max(gaussians2d[t][4], gaussians2d[t][5])): the larger sigma of the projected splat (v,7)
+ * A NULL input leaves its columns untouched.  The rows of a view are distinct, so the update is a plain
+ * read-modify-write without atomics; a list that repeats a row gives undefined sums for that row. */
+int gs_densify_accumulate(int64_t n, int64_t v, const int64_t* points_in_view, const float* grad2d,
+                          int32_t grad2d_stride, const float* heuristic, const float* visibility,
+                          const float* gaussians2d, float* stats, void* stream);
+
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
  * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are

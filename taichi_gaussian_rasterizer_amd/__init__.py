@@ -7,6 +7,7 @@ include/gsplat_hip.h), called through ctypes.  There is no other backend.
 from . import hip_lib, losses, perspective
 from . import hip_lib as cuda_lib  # drop-in alias for `taichi_splatting.cuda_lib`
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
+from .densify import DensifyPlan, DensifyStats, densify, move_rows, plan_densify, split_gaussians3d
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
 from .perspective import CameraParams
 from .rasterizer import RasterOut, rasterize, rasterize_with_tiles
@@ -40,6 +41,7 @@ __all__ = [
     'Gaussians2D', 'Gaussians3D',
     'RasterConfig', 'CameraParams', 'RasterOut',
     'evaluate_sh_at',
+    'DensifyPlan', 'DensifyStats', 'densify', 'move_rows', 'plan_densify', 'split_gaussians3d',
     'rasterize', 'rasterize_with_tiles',
     'perspective', 'hip_lib', 'cuda_lib', 'losses',
     'TaichiQueue', 'taichi_queue',

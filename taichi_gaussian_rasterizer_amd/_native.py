@@ -80,6 +80,16 @@ class GsViewRows(ctypes.Structure):
 GS_VIEWS_MAX = 16  # include/gsplat_hip.h
 
 
+class GsMoveColumn(ctypes.Structure):
+    """include/gsplat_hip.h GsMoveColumn: one column of gs_table_move_rows"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_bytes", c_int32), ("copy_rows", c_int64)]
+
+
+GS_MOVE_COLUMNS_MAX = 32     # include/gsplat_hip.h
+GS_DENSIFY_CHILDREN_MAX = 8
+GS_DENSIFY_STATS = 6
+
+
 # Developer tuning aids (tools/exp_*.py, the wave-region tests): passed per call inside GsRasterConfig; the
 # library itself reads no environment variable.  GS_RASTER_NB / GS_RASTER_HEAVY seed them at import.
 TUNING = {"wave_sub_blocks": int(os.environ.get("GS_RASTER_NB", "0") or 0),
@@ -172,6 +182,12 @@ SIGNATURES = {
     "gs_views_union_scratch_bytes": (_I64, [_I64]),
     "gs_views_union": (ctypes.c_int, [_I64, _I32, POINTER(c_void_p), _P, _P, _P, _I64, _P]),
     "gs_views_sum_rows": (ctypes.c_int, [_I64, _P, _I32, POINTER(GsViewRows), _I32, _P, _P]),
+    # densification: the plan, the move of every per-row table, the children of a 3D split, the statistics
+    "gs_densify_plan_scratch_bytes": (_I64, [_I64]),
+    "gs_densify_plan": (ctypes.c_int, [_I64, _P, _P, _P, _I32, _I64, _P, _P, _P, _I64, _P]),
+    "gs_table_move_rows": (ctypes.c_int, [_I64, _P, _I32, POINTER(GsMoveColumn), _P]),
+    "gs_split3d_children": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _F64, _P, _P, _P]),
+    "gs_densify_accumulate": (ctypes.c_int, [_I64, _I64, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),
