@@ -695,6 +695,29 @@ int gs_densify_accumulate(int64_t n, int64_t v, const int64_t* points_in_view, c
                           int32_t grad2d_stride, const float* heuristic, const float* visibility,
                           const float* gaussians2d, float* stats, void* stream);
 
+/* ------------------------------------------------------------------- Nearest neighbours --
+ * Exact k nearest neighbours of every point of a 3D cloud (the simple-knn step that gives a new Gaussian its first
+ * scale; no counterpart in the reference, whose trainers bring their own).  points (n,3) float32; k in 1 .. GS_KNN_MAX.
+ *   d2(i, j) = (dx * dx + dy * dy) + dz * dz with d = points[j] - points[i], every operation a single float32 operation
+ *   in exactly this order, never contracted: a float32 reimplementation reproduces the result bit for bit.
+ * Row i of dist2 / index (n,k) lists the k points j != i with the smallest (d2, j) in lexicographic order, ascending:
+ * ties in distance go to the smaller index; the point itself is excluded by index, so a duplicate of it is a neighbour
+ * at distance 0.  Entries beyond the n - 1 other points are +inf / -1.  A point with a non-finite coordinate is nobody's
+ * neighbour and its own row is all +inf / -1.  index may be NULL.
+ * Morton codes of the points in their bounding box, gs_radix_sort_pairs, runs of 256 sorted points with one box each;
+ * a wave of 64 queries skips a run whose box is further from the box of its queries than its largest k-th distance
+ * (a bound formed by the same float32 operations, so it never exceeds the d2 of a pair it stands for).
+ * No allocation, no device-to-host copy, no synchronisation: everything is enqueued on `stream`.  scratch:
+ * gs_knn3d_scratch_bytes(n) bytes (0 for n <= 0), 16-byte aligned.  After the call its first ceil(n / 256) int32 hold,
+ * per run of queries, how many (wave, run) pairs were scanned rather than skipped, of 4 * (ceil(n / 256) - 1)
+ * (a diagnostic for benchmarks).
+ * n = 0 returns 0 without touching a pointer.  n < 0, n >= 2^31, k outside 1 .. GS_KNN_MAX, a NULL points / dist2 /
+ * scratch or a misaligned scratch: GS_ERR_INVALID_ARGUMENT; a short scratch: GS_ERR_SCRATCH_TOO_SMALL. */
+#define GS_KNN_MAX 16
+int64_t gs_knn3d_scratch_bytes(int64_t n);
+int gs_knn3d(int64_t n, const float* points, int32_t k, float* dist2, int32_t* index, void* scratch,
+             int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
  * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are

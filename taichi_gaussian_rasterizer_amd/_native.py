@@ -88,6 +88,7 @@ class GsMoveColumn(ctypes.Structure):
 GS_MOVE_COLUMNS_MAX = 32     # include/gsplat_hip.h
 GS_DENSIFY_CHILDREN_MAX = 8
 GS_DENSIFY_STATS = 6
+GS_KNN_MAX = 16
 
 
 # Developer tuning aids (tools/exp_*.py, the wave-region tests): passed per call inside GsRasterConfig; the
@@ -188,6 +189,9 @@ SIGNATURES = {
     "gs_table_move_rows": (ctypes.c_int, [_I64, _P, _I32, POINTER(GsMoveColumn), _P]),
     "gs_split3d_children": (ctypes.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _F64, _P, _P, _P]),
     "gs_densify_accumulate": (ctypes.c_int, [_I64, _I64, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    # nearest neighbours of a point cloud
+    "gs_knn3d_scratch_bytes": (_I64, [_I64]),
+    "gs_knn3d": (ctypes.c_int, [_I64, _P, _I32, _P, _P, _P, _I64, _P]),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),
