@@ -718,6 +718,80 @@ int64_t gs_knn3d_scratch_bytes(int64_t n);
 int gs_knn3d(int64_t n, const float* points, int32_t k, float* dist2, int32_t* index, void* scratch,
              int64_t scratch_bytes, void* stream);
 
+/* --------------------------------------------------------------- MCMC densification --
+ * The fixed-budget strategy of "3D Gaussian Splatting as Markov Chain Monte Carlo" (no counterpart in the reference):
+ * dead rows move onto live rows drawn with probability proportional to opacity, the table grows by the same draw, and
+ * every iteration adds opacity-gated noise to the positions.  The library has no random numbers: the 32-bit words of
+ * the draws and the noise are arguments, so every result is a function of its arguments.
+ *
+ * gs_sample_rows: m weighted draws with replacement from n rows, exact and independent of any summation order.
+ *   q_i   = (uint32) floor(clamp(weights[i], 0, 1) * 2^24); NaN and negative weights give 0, as does a row whose
+ *           exclude byte (n uint8, may be NULL) is non-zero
+ *   cum   = the inclusive prefix sum of q in uint64 (total = cum[n - 1] < 2^55)
+ *   t_j   = floor(random[j] * total / 2^32), the high 64 bits of (random[j] << 32) * total
+ *   out[j] = the first i with cum[i] > t_j: always a row with q_i > 0; random = 2^32 - 1 stays inside the table
+ * select (m uint8, may be NULL; needs m == n): draw j happens only where select[j] is non-zero, elsewhere out[j] = j.
+ * copies (n int32, may be NULL) is zeroed by the call and then counts, with integer atomics, how often each row was
+ * drawn.  total == 0 (no drawable row): every out[j] = j and copies stays 0, so callers see a no-op without a
+ * read-back.  No synchronisation.  scratch: gs_sample_rows_scratch_bytes(n) bytes (0 for n <= 0), 16-byte aligned.
+ * n = m = 0 returns 0 without touching a pointer.  n or m outside 0 .. 2^31 - 1, select with m != n, draws from an
+ * empty table, a NULL weights / scratch (or random / out with m > 0), a misaligned buffer: GS_ERR_INVALID_ARGUMENT; a
+ * short scratch: GS_ERR_SCRATCH_TOO_SMALL. */
+int64_t gs_sample_rows_scratch_bytes(int64_t n);
+int gs_sample_rows(int64_t n, const float* weights, const uint8_t* exclude, int64_t m, const uint32_t* random,
+                   const uint8_t* select, int32_t* out, int32_t* copies, void* scratch, int64_t scratch_bytes,
+                   void* stream);
+
+/* The correction that keeps the rendered result when a Gaussian of opacity o becomes c + 1 of them (itself and its
+ * c = copies[i] copies).  For every row with copies[i] > 0, with n = min(copies[i] + 1, GS_MCMC_N_MAX):
+ *   o_new = clamp(1 - (1 - o)^(1 / n), min_opacity, 1 - 2^-23)
+ *   denom = sum_{i = 1..n} sum_{k = 0..i-1} C(i - 1, k) (-1)^k o_new^(k + 1) / sqrt(k + 1)
+ *   new_alpha_logit[i]   = log(o_new / (1 - o_new))
+ *   new_log_scaling[i][] = log_scaling[i][] + (float) log(o / denom)      (one float32 addition per axis)
+ * evaluated in float64 from the float32 inputs (min_opacity as the double of the float given) and rounded once; the
+ * same sum in float32 is off by 2e-5.  opacity (n), log_scaling (n,3), new_alpha_logit (n), new_log_scaling (n,3).
+ * Rows with copies[i] <= 0 are not written.  min_opacity must lie inside (0, 1). */
+#define GS_MCMC_N_MAX 51
+int gs_mcmc_relocation_values(int64_t n, const float* opacity, const float* log_scaling, const int32_t* copies,
+                              float min_opacity, float* new_alpha_logit, float* new_log_scaling, void* stream);
+
+/* Every output row j < rows_out with copies[src_of[j]] > 0 takes the new values of its source src_of[j]: the source
+ * itself (src_of[j] = j) and all its copies.  Other rows are not written.  out_alpha_logit (rows_out),
+ * out_log_scaling (rows_out,3); src_of[j] must be a row of copies / new_* (not checked). */
+int gs_mcmc_apply(int64_t rows_out, const int32_t* src_of, const int32_t* copies, const float* new_alpha_logit,
+                  const float* new_log_scaling, float* out_alpha_logit, float* out_log_scaling, void* stream);
+
+/* one table of gs_table_relocate_rows: n rows of row_bytes contiguous bytes (a positive multiple of 4; data 4-byte
+ * aligned), changed in place */
+#define GS_RELOCATE_COPY 0          /* a selected row j becomes a copy of row src_of[j] */
+#define GS_RELOCATE_ZERO 1          /* selected rows that moved (src_of[j] != j) and rows with copies > 0 are zeroed */
+#define GS_RELOCATE_ZERO_SOURCES 2  /* only rows with copies > 0 are zero-filled */
+typedef struct GsRelocateColumn {
+  void* data;
+  int32_t row_bytes;
+  int32_t mode;
+} GsRelocateColumn;
+
+/* The in-place counterpart of gs_table_move_rows for up to GS_MOVE_COLUMNS_MAX tables per launch (columns_host: a HOST
+ * array, passed to the kernel by value): select (n uint8), copies (n int32) and src_of (n int32) as gs_sample_rows
+ * leaves them.  No row other than those the column's mode names is written; rows move as bytes.  The contract is that
+ * a selected row is never a source (copies[j] == 0 and no src_of names it), which gs_sample_rows guarantees with
+ * exclude = select: the copy then has no row that is both read and written.  A selected row with
+ * src_of[j] == j drew nothing (the table had no drawable row) and is left alone in every mode.  src_of and select may
+ * be NULL with ZERO_SOURCES columns only, copies with COPY columns only.  Limits as gs_table_move_rows. */
+int gs_table_relocate_rows(int64_t n, const int32_t* src_of, const uint8_t* select, const int32_t* copies,
+                           int32_t columns, const GsRelocateColumn* columns_host, void* stream);
+
+/* The per-iteration noise, in place on position (n,3), all float32:
+ *   q = rotation / |rotation| (xyzw), R(q) as gs_split3d_children builds it; s = exp(log_scaling)
+ *   o = 1 / (1 + exp(-alpha_logit));  g = 1 / (1 + exp(-k ((1 - o) - x0)))
+ *   position += R (s^2 * (R^T (noise * (g * scale))))          scale = lr * noise_lr
+ * A row whose offset is exactly zero keeps its position bits; that covers zero noise and the gate underflowing to 0
+ * (exp overflows: o > 0.89 with k = 100, x0 = 0.995).  Such a row costs its 4 bytes of alpha_logit: nothing else of it
+ * is loaded or stored.  rotation must be 16-byte aligned. */
+int gs_mcmc_perturb(int64_t n, float* position, const float* log_scaling, const float* rotation,
+                    const float* alpha_logit, const float* noise, float scale, float k, float x0, void* stream);
+
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
  * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are

@@ -9,6 +9,7 @@ from . import hip_lib as cuda_lib  # drop-in alias for `taichi_splatting.cuda_li
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .densify import DensifyPlan, DensifyStats, densify, move_rows, plan_densify, split_gaussians3d
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
+from .mcmc import Relocation, grow, perturb, relocate, relocation_values, sample_rows
 from .neighbours import gaussians_from_points, knn
 from .perspective import CameraParams
 from .rasterizer import RasterOut, rasterize, rasterize_with_tiles
@@ -44,6 +45,7 @@ __all__ = [
     'evaluate_sh_at',
     'DensifyPlan', 'DensifyStats', 'densify', 'move_rows', 'plan_densify', 'split_gaussians3d',
     'knn', 'gaussians_from_points',
+    'Relocation', 'grow', 'perturb', 'relocate', 'relocation_values', 'sample_rows',
     'rasterize', 'rasterize_with_tiles',
     'perspective', 'hip_lib', 'cuda_lib', 'losses',
     'TaichiQueue', 'taichi_queue',

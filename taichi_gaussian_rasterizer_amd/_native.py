@@ -85,10 +85,17 @@ class GsMoveColumn(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_bytes", c_int32), ("copy_rows", c_int64)]
 
 
+class GsRelocateColumn(ctypes.Structure):
+    """include/gsplat_hip.h GsRelocateColumn: one table of gs_table_relocate_rows"""
+    _fields_ = [("data", c_void_p), ("row_bytes", c_int32), ("mode", c_int32)]
+
+
 GS_MOVE_COLUMNS_MAX = 32     # include/gsplat_hip.h
 GS_DENSIFY_CHILDREN_MAX = 8
 GS_DENSIFY_STATS = 6
 GS_KNN_MAX = 16
+GS_MCMC_N_MAX = 51
+GS_RELOCATE_COPY, GS_RELOCATE_ZERO, GS_RELOCATE_ZERO_SOURCES = range(3)
 
 
 # Developer tuning aids (tools/exp_*.py, the wave-region tests): passed per call inside GsRasterConfig; the
@@ -192,6 +199,13 @@ SIGNATURES = {
     # nearest neighbours of a point cloud
     "gs_knn3d_scratch_bytes": (_I64, [_I64]),
     "gs_knn3d": (ctypes.c_int, [_I64, _P, _I32, _P, _P, _P, _I64, _P]),
+    # MCMC densification: exact weighted draws, the relocation correction, in-place row surgery, the position noise
+    "gs_sample_rows_scratch_bytes": (_I64, [_I64]),
+    "gs_sample_rows": (ctypes.c_int, [_I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "gs_mcmc_relocation_values": (ctypes.c_int, [_I64, _P, _P, _P, c_float, _P, _P, _P]),
+    "gs_mcmc_apply": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_table_relocate_rows": (ctypes.c_int, [_I64, _P, _P, _P, _I32, POINTER(GsRelocateColumn), _P]),
+    "gs_mcmc_perturb": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P]),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),
