@@ -962,6 +962,54 @@ int gs_photo_loss_weighted_bwd_f64(int64_t batch, int64_t height, int64_t width,
                                    const double* saved_maps, const double* upstream_map, const double* grad_loss,
                                    double l1_coeff, double ssim_coeff, double* d_image, void* stream);
 
+/* ------------------------------------------------ appearance: slicing a bilateral grid (bilagrid.hip) --
+ * Per-image colour correction: a grid (batch, 12, grid_l, grid_h, grid_w) of 3x4 affine colour transforms, channel
+ * 4 r + c = element (r, c), each batch entry contiguous and `grid_batch_stride` ELEMENTS from the one before (the
+ * layout torch's grid_sample takes), sliced at every pixel of a channel-last image (batch, height, width, 3).  For the
+ * pixel at column x, row y with colour rgb:
+ *   guide = 0.299 r + 0.587 g + 0.114 b, or guide[y, x] when `guide` (batch, height, width) is not NULL
+ *   gx = (x + 0.5) / width * (grid_w - 1),  gy = (y + 0.5) / height * (grid_h - 1),  gz = clamp(guide, 0, 1) * (grid_l - 1)
+ *   A = trilinear interpolation of the 12 channels at (gz, gy, gx), cell = min(floor(coord), size - 2), 0 for size 1
+ *   out = A[:, :3] rgb + A[:, 3]
+ * which is grid_sample(mode = bilinear, padding_mode = border, align_corners = True) followed by the affine.  The
+ * interpolation is a + (b - a) f along each axis, so an identity grid returns the image bit for bit.  A 1 x 1 x 1
+ * grid is one affine colour matrix per image.
+ * image and guide are read through a batch, a row and a pixel stride in ELEMENTS (channels contiguous; pixel stride >=
+ * 3 for the image, >= 1 for the guide; row stride >= width * pixel stride; batch stride >= height * row stride).
+ * Forward: out (batch, height, width, 3), contiguous.
+ * Backward: grad_out as out; d_image (as out), d_guide (batch, height, width; only with a guide) and d_grid (as the
+ * grid, contiguous) are written, not accumulated; each may be NULL, not all.  d_image holds the gradient through the
+ * affine and, without a guide, through the luma; the gradient through gz is zero where the guide is not inside (0, 1).
+ * d_grid needs scratch (gs_bilagrid_scratch_bytes, 8-byte aligned; f64 != 0 for the _f64 call): every pixel tile's
+ * sums, which a second launch adds in tile order.  Every output of both directions repeats bit for bit.
+ * Sizes must be positive (-1).  Any shape with grid_l <= 16 is accepted; the call returns -2 when the 2 x 2 x grid_l
+ * nodes around one pixel do not fit in LDS twice (grid_l above 85 in float64), and above 2^22 pixels a side, 2^31 grid
+ * elements or 2^31 pixel tiles.  gs_bilagrid_scratch_bytes returns the same negative codes. */
+int64_t gs_bilagrid_scratch_bytes(int64_t batch, int64_t height, int64_t width, int64_t grid_l, int64_t grid_h,
+                                  int64_t grid_w, int32_t f64);
+int gs_bilagrid_slice_fwd(int64_t batch, int64_t height, int64_t width, const float* image,
+                          int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                          const float* guide, int64_t guide_batch_stride, int64_t guide_row_stride,
+                          int64_t guide_pixel_stride, const float* grid, int64_t grid_l, int64_t grid_h,
+                          int64_t grid_w, int64_t grid_batch_stride, float* out, void* stream);
+int gs_bilagrid_slice_bwd(int64_t batch, int64_t height, int64_t width, const float* image,
+                          int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                          const float* guide, int64_t guide_batch_stride, int64_t guide_row_stride,
+                          int64_t guide_pixel_stride, const float* grid, int64_t grid_l, int64_t grid_h,
+                          int64_t grid_w, int64_t grid_batch_stride, const float* grad_out, float* d_image,
+                          float* d_guide, float* d_grid, void* scratch, int64_t scratch_bytes, void* stream);
+int gs_bilagrid_slice_fwd_f64(int64_t batch, int64_t height, int64_t width, const double* image,
+                              int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                              const double* guide, int64_t guide_batch_stride, int64_t guide_row_stride,
+                              int64_t guide_pixel_stride, const double* grid, int64_t grid_l, int64_t grid_h,
+                              int64_t grid_w, int64_t grid_batch_stride, double* out, void* stream);
+int gs_bilagrid_slice_bwd_f64(int64_t batch, int64_t height, int64_t width, const double* image,
+                              int64_t image_batch_stride, int64_t image_row_stride, int64_t image_pixel_stride,
+                              const double* guide, int64_t guide_batch_stride, int64_t guide_row_stride,
+                              int64_t guide_pixel_stride, const double* grid, int64_t grid_l, int64_t grid_h,
+                              int64_t grid_w, int64_t grid_batch_stride, const double* grad_out, double* d_image,
+                              double* d_guide, double* d_grid, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ operator API of taichi_splatting (reference taichi_splatting/__init__.py:1-33).
 Compute backend: hand-written HIP kernels for gfx950 in libgsplat_hip.so (C-ABI:
 include/gsplat_hip.h), called through ctypes.  There is no other backend.
 """
-from . import hip_lib, losses, perspective
+from . import appearance, hip_lib, losses, perspective
 from . import hip_lib as cuda_lib  # drop-in alias for `taichi_splatting.cuda_lib`
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .densify import DensifyPlan, DensifyStats, densify, move_rows, plan_densify, split_gaussians3d
@@ -47,7 +47,7 @@ __all__ = [
     'knn', 'gaussians_from_points',
     'Relocation', 'grow', 'perturb', 'relocate', 'relocation_values', 'sample_rows',
     'rasterize', 'rasterize_with_tiles',
-    'perspective', 'hip_lib', 'cuda_lib', 'losses',
+    'perspective', 'hip_lib', 'cuda_lib', 'losses', 'appearance',
     'TaichiQueue', 'taichi_queue',
     'install_as_taichi_splatting',
 ]

@@ -243,6 +243,15 @@ SIGNATURES = {
     "gs_photo_loss_weighted_bwd_f64": (ctypes.c_int, [_I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64,
                                                        _I64, _P, _I64, _I64, _I64, _P, _I32, _F64, _I32, _P, _P, _P,
                                                        _F64, _F64, _P, _P]),
+    # appearance: a bilateral grid of colour transforms sliced at every pixel (image and guide with three strides each,
+    # the grid with its sizes and batch stride)
+    "gs_bilagrid_scratch_bytes": (_I64, [_I64] * 6 + [_I32]),
+    "gs_bilagrid_slice_fwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 2 + [_P] + [_I64] * 4 + [_P, _P]),
+    "gs_bilagrid_slice_bwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 2 + [_P] + [_I64] * 4 + [_P] * 5 +
+                              [_I64, _P]),
+    "gs_bilagrid_slice_fwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 2 + [_P] + [_I64] * 4 + [_P, _P]),
+    "gs_bilagrid_slice_bwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 2 + [_P] + [_I64] * 4 +
+                                  [_P] * 5 + [_I64, _P]),
 }
 
 _lib = None
