@@ -792,6 +792,58 @@ int gs_table_relocate_rows(int64_t n, const int32_t* src_of, const uint8_t* sele
 int gs_mcmc_perturb(int64_t n, float* position, const float* log_scaling, const float* rotation,
                     const float* alpha_logit, const float* noise, float scale, float k, float x0, void* stream);
 
+/* --------------------------------------------------- Mip-Splatting: the 3D smoothing filter (mip.hip) --
+ * The world-space half of Mip-Splatting (no counterpart in the reference): every Gaussian is low-passed with an
+ * isotropic Gaussian sized by the highest rate at which any training camera samples it, and its opacity rescaled so
+ * that it keeps its mass.
+ *
+ * gs_mip_sampling_rate: position (n,3) float32; packed: a device table of `cameras` records of GS_MIP_CAMERA_FLOATS
+ * float32 each:
+ *   [0..11]  rows 0-2 of T_camera_world, row-major        [12..15] fx, fy, cx, cy
+ *   [16..19] lo_x, hi_x, lo_y, hi_y = -m W, (1 + m) W, -m H, (1 + m) H for a margin m, rounded to float32 by the host
+ *   [20] near plane   [21] far plane   [22] focal = max(fx, fy)   [23] 0
+ * For point p and camera c, every product and sum its own float32 rounding, in this order, never contracted:
+ *   xc = ((T00*px + T01*py) + T02*pz) + T03          (yc, zc likewise from rows 1, 2)
+ *   u  = fx*xc + cx*zc        v = fy*yc + cy*zc
+ *   valid = zc >= near && zc <= far && lo_x*zc <= u && u <= hi_x*zc && lo_y*zc <= v && v <= hi_y*zc
+ * A NaN makes a comparison false: a non-finite point is never valid.  rate[i] (n float32) = the maximum over the valid
+ * cameras of the correctly rounded focal / zc, 0 when there is none (the largest f / d, the paper's definition; not the
+ * smallest depth times one global focal length); seen[i] (n int32) = the number of valid cameras.  A float32
+ * restatement reproduces both bit for bit.  One launch, no scratch, no synchronisation.
+ * n = 0 returns 0 without touching a pointer.  n < 0, n >= 2^31, cameras outside 0 .. GS_MIP_CAMERAS_MAX, a NULL
+ * position / rate / seen (or packed with cameras > 0), a pointer not 4-byte aligned: GS_ERR_INVALID_ARGUMENT. */
+#define GS_MIP_CAMERA_FLOATS 24
+#define GS_MIP_CAMERAS_MAX 65536
+int gs_mip_sampling_rate(int64_t n, const float* position, int32_t cameras, const float* packed, float* rate,
+                         int32_t* seen, void* stream);
+
+/* gs_smooth3d_*: per row l = log_scaling (n,3), a = alpha_logit (n), f = filter3d (n) >= 0, a constant:
+ *   x_k = f^2 e^{-2 l_k}     l'_k = log(e^{2 l_k} + f^2) / 2     log c = -sum_k log1p(x_k) / 2     a' = logit(sigmoid(a) c)
+ *   dL/dl_k = g_l'_k / (1 + x_k) + g_a' x_k / (1 + x_k) / (1 - sigmoid(a) c)        dL/da = g_a' / (1 + e^a (1 - c))
+ * i.e. scale' = sqrt(scale^2 + f^2) and opacity' = opacity sqrt(det S / det S').  Evaluated in forms that hold for
+ * |l|, |a| <= 40 and f in 0 .. 1e6 (head of mip.hip): every output is finite there.  A row with f == 0 returns l, a and
+ * both incoming gradients bit for bit.  The forward saves nothing; the backward recomputes from (l, a, f).
+ * Dense backward: grad_log_scaling (n,3), grad_alpha_logit (n), either may be NULL (zero); d_log_scaling (n,3) and
+ * d_alpha_logit (n) are written.  Row-compact backward: rows (v int64, rows of the n as a frame's sparse gradient lists
+ * them), gradients and outputs (v,3), (v); nothing of size n is written or allocated, a row index outside [0, n) gives
+ * a zero row.  The two forms run the same device function and agree bit for bit.  The _f64 forms are the same templated
+ * source in double (for gradcheck).  Outputs must not alias inputs.
+ * n = 0 (v = 0) returns 0 without touching a pointer.  n or v outside 0 .. 2^31 - 1, v > 0 with n = 0, a NULL buffer
+ * other than an incoming gradient, a pointer not aligned to its element: GS_ERR_INVALID_ARGUMENT. */
+int gs_smooth3d_fwd(int64_t n, const float* log_scaling, const float* alpha_logit, const float* filter3d,
+                    float* out_log_scaling, float* out_alpha_logit, void* stream);
+int gs_smooth3d_bwd(int64_t n, const float* log_scaling, const float* alpha_logit, const float* filter3d,
+                    const float* grad_log_scaling, const float* grad_alpha_logit, float* d_log_scaling,
+                    float* d_alpha_logit, void* stream);
+int gs_smooth3d_bwd_rows(int64_t n, int64_t v, const int64_t* rows, const float* log_scaling,
+                         const float* alpha_logit, const float* filter3d, const float* grad_log_scaling,
+                         const float* grad_alpha_logit, float* d_log_scaling, float* d_alpha_logit, void* stream);
+int gs_smooth3d_fwd_f64(int64_t n, const double* log_scaling, const double* alpha_logit, const double* filter3d,
+                        double* out_log_scaling, double* out_alpha_logit, void* stream);
+int gs_smooth3d_bwd_f64(int64_t n, const double* log_scaling, const double* alpha_logit, const double* filter3d,
+                        const double* grad_log_scaling, const double* grad_alpha_logit, double* d_log_scaling,
+                        double* d_alpha_logit, void* stream);
+
 /* ------------------------------------------------------------------- float64 operators --
  * The projection, SH and rasterizer in float64, for gradcheck (the reference builds these stages for f64 too,
  * rasterizer/function.py:122, perspective/projection.py:27, spherical_harmonics.py:24-27).  Projection and SH are

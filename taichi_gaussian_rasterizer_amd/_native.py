@@ -95,6 +95,8 @@ GS_DENSIFY_CHILDREN_MAX = 8
 GS_DENSIFY_STATS = 6
 GS_KNN_MAX = 16
 GS_MCMC_N_MAX = 51
+GS_MIP_CAMERA_FLOATS = 24
+GS_MIP_CAMERAS_MAX = 65536
 GS_RELOCATE_COPY, GS_RELOCATE_ZERO, GS_RELOCATE_ZERO_SOURCES = range(3)
 
 
@@ -206,6 +208,13 @@ SIGNATURES = {
     "gs_mcmc_apply": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _P]),
     "gs_table_relocate_rows": (ctypes.c_int, [_I64, _P, _P, _P, _I32, POINTER(GsRelocateColumn), _P]),
     "gs_mcmc_perturb": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P]),
+    # Mip-Splatting's 3D smoothing filter: the sampling rate over a camera table, the low-pass and its two backwards
+    "gs_mip_sampling_rate": (ctypes.c_int, [_I64, _P, _I32, _P, _P, _P, _P]),
+    "gs_smooth3d_fwd": (ctypes.c_int, [_I64] + [_P] * 6),
+    "gs_smooth3d_bwd": (ctypes.c_int, [_I64] + [_P] * 8),
+    "gs_smooth3d_bwd_rows": (ctypes.c_int, [_I64, _I64] + [_P] * 9),
+    "gs_smooth3d_fwd_f64": (ctypes.c_int, [_I64] + [_P] * 6),
+    "gs_smooth3d_bwd_f64": (ctypes.c_int, [_I64] + [_P] * 8),
     "gs_project_f64_scratch_bytes": (_I64, [_I64]),
     "gs_project_fwd_f64": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _F64, _F64, _CFG64, _P, _P, _P, _P,
                                            _P, _P, _P, _I64, _P]),
