@@ -1062,6 +1062,50 @@ int gs_bilagrid_slice_bwd_f64(int64_t batch, int64_t height, int64_t width, cons
                               int64_t grid_w, int64_t grid_batch_stride, const double* grad_out, double* d_image,
                               double* d_guide, double* d_grid, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* -------------------------------------------- environment: a cubemap sky behind the render (envmap.hip) --
+ * A learnable environment map env (6, map_edge, map_edge, channels), channel-last and contiguous, channels in 1 .. 4,
+ * looked up by the view direction of every pixel of a pinhole camera and composited behind a render.  The camera is
+ * read on the device: projection = (fx, fy, cx, cy) and T_camera_world = the 4x4 world -> camera matrix, row-major;
+ * nothing is read back.  For the pixel at column x, row y (R = map_edge):
+ *   d_cam = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1),  d = Rcw^T d_cam,  Rcw = T_camera_world[:3, :3], taken as a
+ *           rotation: the map is at infinity and the translation is not read
+ *   a = the axis of the largest |d_i|, ties to the lower index;  face = 2 a + (d_a < 0)
+ *   (p, q) = the two other components in ascending axis order, divided by |d_a|   (a = 0: y, z; a = 1: x, z; a = 2: x, y)
+ *   u = clamp((p + 1) / 2 * R - 0.5, 0, R - 1) (column),  v = clamp((q + 1) / 2 * R - 0.5, 0, R - 1) (row)
+ *   sky = bilinear interpolation of env[face] at (v, u), taps clamped inside the face
+ *   out = image + (1 - weight) * sky
+ * which is grid_sample(bilinear, border, align_corners = False) on the chosen face.  No sign flips between faces and
+ * no filtering across face seams.  A constant map returns the constant bit for bit, weight == 1 the image bit for bit.
+ * image (height, width, channels) and weight (height, width) are read through a row and a pixel stride in ELEMENTS
+ * (channels contiguous; pixel stride >= channels for the image, >= 1 for the weight; row stride >= width * pixel
+ * stride).  They are NULL together: the sky alone.  Forward: out (height, width, channels), contiguous.
+ * Backward: grad_out as out.  d_image is grad_out itself and has no kernel.  d_weight (height, width) = -sum_c
+ * grad_out_c sky_c, needs weight and env.  d_env (as env, contiguous) is written, not accumulated, exactly zero where
+ * no pixel looks: a gather with one sum per texel in an order the shapes fix, no atomics -- every output repeats bit
+ * for bit.  d_weight and d_env may each be NULL, not both.  The view direction is not differentiated: no gradient for
+ * projection or T_camera_world.  d_env may need scratch (gs_envmap_scratch_bytes, 8-byte aligned; f64 != 0 for the
+ * _f64 calls; 0 bytes for most shapes).
+ * Sizes below 1 or a NULL buffer where none is allowed: -1; channels outside 1 .. 4, map_edge above 16384 or an image
+ * of 2^31 pixels or more: -2; a short scratch: -4; all before any launch.  gs_envmap_scratch_bytes returns the same
+ * negative codes. */
+int64_t gs_envmap_scratch_bytes(int64_t height, int64_t width, int64_t channels, int64_t map_edge, int32_t f64);
+int gs_envmap_fwd(int64_t height, int64_t width, int64_t channels, const float* env, int64_t map_edge,
+                  const float* image, int64_t image_row_stride, int64_t image_pixel_stride, const float* weight,
+                  int64_t weight_row_stride, int64_t weight_pixel_stride, const float* projection,
+                  const float* T_camera_world, float* out, void* stream);
+int gs_envmap_bwd(int64_t height, int64_t width, int64_t channels, const float* env, int64_t map_edge,
+                  const float* weight, int64_t weight_row_stride, int64_t weight_pixel_stride, const float* projection,
+                  const float* T_camera_world, const float* grad_out, float* d_weight, float* d_env, void* scratch,
+                  int64_t scratch_bytes, void* stream);
+int gs_envmap_fwd_f64(int64_t height, int64_t width, int64_t channels, const double* env, int64_t map_edge,
+                      const double* image, int64_t image_row_stride, int64_t image_pixel_stride, const double* weight,
+                      int64_t weight_row_stride, int64_t weight_pixel_stride, const double* projection,
+                      const double* T_camera_world, double* out, void* stream);
+int gs_envmap_bwd_f64(int64_t height, int64_t width, int64_t channels, const double* env, int64_t map_edge,
+                      const double* weight, int64_t weight_row_stride, int64_t weight_pixel_stride,
+                      const double* projection, const double* T_camera_world, const double* grad_out, double* d_weight,
+                      double* d_env, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

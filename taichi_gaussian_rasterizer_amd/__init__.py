@@ -4,10 +4,11 @@ operator API of taichi_splatting (reference taichi_splatting/__init__.py:1-33).
 Compute backend: hand-written HIP kernels for gfx950 in libgsplat_hip.so (C-ABI:
 include/gsplat_hip.h), called through ctypes.  There is no other backend.
 """
-from . import appearance, hip_lib, losses, mip, perspective
+from . import appearance, environment, hip_lib, losses, mip, perspective
 from . import hip_lib as cuda_lib  # drop-in alias for `taichi_splatting.cuda_lib`
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
 from .densify import DensifyPlan, DensifyStats, densify, move_rows, plan_densify, split_gaussians3d
+from .environment import composite_environment, constant_environment, environment_directions, sample_environment
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
 from .mcmc import Relocation, grow, perturb, relocate, relocation_values, sample_rows
 from .mip import filter_3d, pack_cameras, sampling_rate, smooth3d, smooth_gaussians
@@ -50,6 +51,7 @@ __all__ = [
     'mip', 'filter_3d', 'pack_cameras', 'sampling_rate', 'smooth3d', 'smooth_gaussians',
     'rasterize', 'rasterize_with_tiles',
     'perspective', 'hip_lib', 'cuda_lib', 'losses', 'appearance',
+    'environment', 'composite_environment', 'sample_environment', 'environment_directions', 'constant_environment',
     'TaichiQueue', 'taichi_queue',
     'install_as_taichi_splatting',
 ]

@@ -261,6 +261,13 @@ SIGNATURES = {
     "gs_bilagrid_slice_fwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 2 + [_P] + [_I64] * 4 + [_P, _P]),
     "gs_bilagrid_slice_bwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 2 + [_P] + [_I64] * 4 +
                                   [_P] * 5 + [_I64, _P]),
+    # environment: a cubemap sky behind the render (env and its edge, image and weight with two strides each, the
+    # camera's two device tensors)
+    "gs_envmap_scratch_bytes": (_I64, [_I64] * 4 + [_I32]),
+    "gs_envmap_fwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] * 2 + [_P] * 4),
+    "gs_envmap_bwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] + [_P] * 6 + [_I64, _P]),
+    "gs_envmap_fwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] * 2 + [_P] * 4),
+    "gs_envmap_bwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] + [_P] * 6 + [_I64, _P]),
 }
 
 _lib = None

@@ -188,7 +188,8 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
     channels of render_depth do not count).  The returned image is composited on it inside the rasterizer, image =
     blend + (1 - image_weight) * background; image_weight itself does not change.  It may require grad and then
     receives dL/dbackground.  (A per-pixel background is composited by the caller in torch -- correctly once
-    differentiable_weight is set.)  differentiable_weight=True: image_weight takes part in autograd, so alpha, mask and
+    differentiable_weight is set; a learnable cubemap sky looked up by view direction is
+    environment.composite_environment.)  differentiable_weight=True: image_weight takes part in autograd, so alpha, mask and
     sky losses reach the Gaussians.  `depth` and `depth_var` of render_depth keep treating the weight in their divisor
     as a constant, and are the same with and without a background; the median-depth pass has no background.  Both
     arguments need config.use_alpha_blending (ValueError); a background of another dtype or device raises TypeError,
