@@ -446,26 +446,20 @@ int bg_image(const char* who, const char* name, int channels, int64_t batch, int
   return GS_OK;
 }
 
-#define BG_TRY(expr)              \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_ != GS_OK) return rc_; \
-  } while (0)
-
 // what both directions check and fill alike
 template <typename T>
 int bg_common(const char* who, int64_t batch, int64_t height, int64_t width, const T* image, int64_t isb, int64_t isr,
               int64_t isp, const T* guide, int64_t gsb, int64_t gsr, int64_t gsp, const T* grid, int64_t L, int64_t Hg,
               int64_t Wg, int64_t grid_sb, BgArgs<T>* a, BgPlan* plan) {
-  BG_TRY(bg_sizes(who, batch, height, width, L, Hg, Wg));
+  GS_TRY(bg_sizes(who, batch, height, width, L, Hg, Wg));
   GS_REQUIRE(image != nullptr && grid != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (image / grid)", who);
-  BG_TRY(bg_image(who, "image", 3, batch, height, width, image, isb, isr, isp, &a->x));
+  GS_TRY(bg_image(who, "image", 3, batch, height, width, image, isb, isr, isp, &a->x));
   a->guide = BgImage<T>{nullptr, 0, 0, 0};
-  if (guide) BG_TRY(bg_image(who, "guide", 1, batch, height, width, guide, gsb, gsr, gsp, &a->guide));
+  if (guide) GS_TRY(bg_image(who, "guide", 1, batch, height, width, guide, gsb, gsr, gsp, &a->guide));
   GS_REQUIRE(batch <= 1 || grid_sb >= BG_CH * L * Hg * Wg, GS_ERR_INVALID_ARGUMENT,
              "%s: grid batch stride %lld below the %lld elements of one grid", who, (long long)grid_sb,
              (long long)(BG_CH * L * Hg * Wg));
-  BG_TRY(bg_plan<T>(who, batch, height, width, L, Hg, Wg, plan));
+  GS_TRY(bg_plan<T>(who, batch, height, width, L, Hg, Wg, plan));
   a->batch = int(batch); a->height = int(height); a->width = int(width);
   a->L = int(L); a->Hg = int(Hg); a->Wg = int(Wg);
   a->tile = plan->tile; a->tile_shift = plan->tile_shift; a->tiles_x = plan->tiles_x; a->tiles_y = plan->tiles_y;
@@ -482,7 +476,7 @@ int bg_fwd(const char* who, int64_t batch, int64_t height, int64_t width, const 
            int64_t Wg, int64_t grid_sb, T* out, void* stream) {
   BgArgs<T> a;
   BgPlan plan;
-  BG_TRY(bg_common(who, batch, height, width, image, isb, isr, isp, guide, gsb, gsr, gsp, grid, L, Hg, Wg, grid_sb, &a,
+  GS_TRY(bg_common(who, batch, height, width, image, isb, isr, isp, guide, gsb, gsr, gsp, grid, L, Hg, Wg, grid_sb, &a,
                    &plan));
   GS_REQUIRE(out != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (out)", who);
   a.out = out;
@@ -503,7 +497,7 @@ int bg_bwd(const char* who, int64_t batch, int64_t height, int64_t width, const 
            int64_t scratch_bytes, void* stream) {
   BgArgs<T> a;
   BgPlan plan;
-  BG_TRY(bg_common(who, batch, height, width, image, isb, isr, isp, guide, gsb, gsr, gsp, grid, L, Hg, Wg, grid_sb, &a,
+  GS_TRY(bg_common(who, batch, height, width, image, isb, isr, isp, guide, gsb, gsr, gsp, grid, L, Hg, Wg, grid_sb, &a,
                    &plan));
   GS_REQUIRE(grad_out != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (grad_out)", who);
   GS_REQUIRE(d_image || d_guide || d_grid, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (no gradient asked for)", who);
@@ -511,12 +505,7 @@ int bg_bwd(const char* who, int64_t batch, int64_t height, int64_t width, const 
   if (d_grid) {
     GS_REQUIRE(batch * L * Hg * Wg < (int64_t(1) << 31), GS_ERR_UNSUPPORTED,
                "%s: %lld grid nodes above the launch limit 2^31", who, (long long)(batch * L * Hg * Wg));
-    GS_REQUIRE(scratch != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (scratch)", who);
-    GS_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, GS_ERR_INVALID_ARGUMENT,
-               "%s: scratch must be 8-byte aligned", who);
-    const int64_t need = bg_scratch_bytes<T>(plan);
-    GS_REQUIRE(scratch_bytes >= need, GS_ERR_SCRATCH_TOO_SMALL, "%s: scratch %lld < %lld bytes", who,
-               (long long)scratch_bytes, (long long)need);
+    GS_TRY(gs_check_scratch(who, scratch, scratch_bytes, bg_scratch_bytes<T>(plan)));
     a.partials = static_cast<T*>(scratch);
   }
   a.grad_out = grad_out; a.d_image = d_image; a.d_guide = d_guide;
@@ -538,12 +527,12 @@ extern "C" int64_t gs_bilagrid_scratch_bytes(int64_t batch, int64_t height, int6
                                               int64_t grid_h, int64_t grid_w, int32_t f64) {
   const char* who = "gs_bilagrid_scratch_bytes";
   BgPlan plan;
-  BG_TRY(bg_sizes(who, batch, height, width, grid_l, grid_h, grid_w));
+  GS_TRY(bg_sizes(who, batch, height, width, grid_l, grid_h, grid_w));
   if (f64) {
-    BG_TRY(bg_plan<double>(who, batch, height, width, grid_l, grid_h, grid_w, &plan));
+    GS_TRY(bg_plan<double>(who, batch, height, width, grid_l, grid_h, grid_w, &plan));
     return bg_scratch_bytes<double>(plan);
   }
-  BG_TRY(bg_plan<float>(who, batch, height, width, grid_l, grid_h, grid_w, &plan));
+  GS_TRY(bg_plan<float>(who, batch, height, width, grid_l, grid_h, grid_w, &plan));
   return bg_scratch_bytes<float>(plan);
 }
 

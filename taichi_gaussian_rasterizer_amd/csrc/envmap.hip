@@ -375,16 +375,10 @@ int64_t env_scratch_bytes(const EnvPlan& p, int64_t channels, int64_t R, size_t 
   return p.slices > 1 ? 6 * R * R * p.slices * channels * int64_t(elem) : 0;
 }
 
-#define ENV_TRY(expr)             \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_ != GS_OK) return rc_; \
-  } while (0)
-
 template <typename T>
 int env_common(const char* who, int64_t height, int64_t width, int64_t channels, const T* env, int64_t R,
                const T* weight, int64_t wsr, int64_t wsp, const T* projection, const T* pose, EnvArgs<T>* a) {
-  ENV_TRY(env_sizes(who, height, width, channels, R));
+  GS_TRY(env_sizes(who, height, width, channels, R));
   GS_REQUIRE(projection != nullptr && pose != nullptr, GS_ERR_INVALID_ARGUMENT,
              "%s: NULL buffer (projection / T_camera_world)", who);
   if (weight)
@@ -424,7 +418,7 @@ int env_fwd(const char* who, int64_t height, int64_t width, int64_t channels, co
             int64_t isr, int64_t isp, const T* weight, int64_t wsr, int64_t wsp, const T* projection, const T* pose,
             T* out, void* stream) {
   EnvArgs<T> a;
-  ENV_TRY(env_common(who, height, width, channels, env, R, weight, wsr, wsp, projection, pose, &a));
+  GS_TRY(env_common(who, height, width, channels, env, R, weight, wsr, wsp, projection, pose, &a));
   GS_REQUIRE(env != nullptr && out != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (env / out)", who);
   GS_REQUIRE((image == nullptr) == (weight == nullptr), GS_ERR_INVALID_ARGUMENT,
              "%s: image and weight go together (both, or both NULL for the sky alone)", who);
@@ -443,7 +437,7 @@ int env_bwd(const char* who, int64_t height, int64_t width, int64_t channels, co
             int64_t wsr, int64_t wsp, const T* projection, const T* pose, const T* grad_out, T* d_weight, T* d_env,
             void* scratch, int64_t scratch_bytes, void* stream) {
   EnvArgs<T> a;
-  ENV_TRY(env_common(who, height, width, channels, env, R, weight, wsr, wsp, projection, pose, &a));
+  GS_TRY(env_common(who, height, width, channels, env, R, weight, wsr, wsp, projection, pose, &a));
   GS_REQUIRE(grad_out != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (grad_out)", who);
   GS_REQUIRE(d_weight || d_env, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (no gradient asked for)", who);
   GS_REQUIRE(!d_weight || (weight && env), GS_ERR_INVALID_ARGUMENT, "%s: d_weight without a weight or without env",
@@ -454,11 +448,7 @@ int env_bwd(const char* who, int64_t height, int64_t width, int64_t channels, co
                who, (long long)plan.blocks);
     const int64_t need = env_scratch_bytes(plan, channels, R, sizeof(T));
     if (need > 0) {
-      GS_REQUIRE(scratch != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (scratch)", who);
-      GS_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, GS_ERR_INVALID_ARGUMENT,
-                 "%s: scratch must be 8-byte aligned", who);
-      GS_REQUIRE(scratch_bytes >= need, GS_ERR_SCRATCH_TOO_SMALL, "%s: scratch %lld < %lld bytes", who,
-                 (long long)scratch_bytes, (long long)need);
+      GS_TRY(gs_check_scratch(who, scratch, scratch_bytes, need));
       a.partials = static_cast<T*>(scratch);
     }
     a.slices = plan.slices;
@@ -490,7 +480,7 @@ int env_bwd(const char* who, int64_t height, int64_t width, int64_t channels, co
 
 extern "C" int64_t gs_envmap_scratch_bytes(int64_t height, int64_t width, int64_t channels, int64_t map_edge,
                                             int32_t f64) {
-  ENV_TRY(env_sizes("gs_envmap_scratch_bytes", height, width, channels, map_edge));
+  GS_TRY(env_sizes("gs_envmap_scratch_bytes", height, width, channels, map_edge));
   return env_scratch_bytes(env_plan(height, width, map_edge), channels, map_edge, f64 ? sizeof(double) : sizeof(float));
 }
 

@@ -76,6 +76,23 @@ static inline int gs_check_raster_fwd_buffers(const char* what, const void* imag
   return GS_OK;
 }
 
+// ---- what the host side of the image-space units (loss, bilagrid, envmap) refuses alike
+#define GS_TRY(expr)              \
+  do {                            \
+    const int rc_ = (expr);       \
+    if (rc_ != GS_OK) return rc_; \
+  } while (0)
+
+// a caller's scratch buffer of at least `need` bytes
+static inline int gs_check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need) {
+  GS_REQUIRE(scratch != nullptr, GS_ERR_INVALID_ARGUMENT, "%s: NULL buffer (scratch)", who);
+  GS_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, GS_ERR_INVALID_ARGUMENT,
+             "%s: scratch must be 8-byte aligned", who);
+  GS_REQUIRE(scratch_bytes >= need, GS_ERR_SCRATCH_TOO_SMALL, "%s: scratch %lld < %lld bytes", who,
+             (long long)scratch_bytes, (long long)need);
+  return GS_OK;
+}
+
 // ---- screen-tile sharding (GsRowShard, include/gsplat_hip.h): owned tile rows <-> local rows.  Plain struct
 // arithmetic, usable on host and device.  `rows` = tile rows of the full image.
 struct GsShard {
