@@ -1106,6 +1106,60 @@ int gs_envmap_bwd_f64(int64_t height, int64_t width, int64_t channels, const dou
                       const double* projection, const double* T_camera_world, const double* grad_out, double* d_weight,
                       double* d_env, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------- depth: losses against a depth prior with a per-image fit (depth_loss.hip) --
+ * depth and prior (batch, height, width), weight the same or NULL (every weight 1), each read through a batch, a row and
+ * a pixel stride in ELEMENTS (pixel stride >= 1, row stride >= width * pixel stride, batch stride >= height * row
+ * stride; the weight's batch stride may be 0: one weight for every image).  Per image b, with x = depth, or 1 / depth
+ * when inverse = 1, p = prior, over the pixels that are not SELECTED OUT -- a pixel is selected out, adds nothing to
+ * any sum whatever it holds and gets a gradient of exactly 0, when its weight is not > 0, its depth or prior is not
+ * finite, or inverse = 1 and its depth is <= 0:
+ *   W = sum w, pm = sum w p / W, xm = sum w x / W, var_p = sum w (p - pm)^2, cov = sum w (p - pm)(x - xm), var_x likewise
+ *   kind 0 (L1)       r = x - s p - t,  L_b = sum w |r| / W,  loss = mean over b of L_b, with
+ *     align 0 (affine)  s = cov / var_p, t = xm - s pm;  var_p <= 1e-12 sum w p^2:  s = 0, t = xm
+ *     align 1 (scale)   s = sum w p x / sum w p^2, t = 0;  sum w p^2 = 0:  s = 0
+ *     align 2 (none)    s = 1, t = 0
+ *   kind 1 (Pearson)  rho_b = cov / sqrt(var_p var_x), loss = mean over b of 1 - rho_b;  rho_b = 0 with zero gradient
+ *                     when W = 0, var_p <= 1e-12 sum w p^2 or var_x <= 1e-12 sum w x^2
+ *   kind 2 (fit)      s and t of the align alone; forward only
+ * results holds 1 + 3 batch values: the loss (0 for kind 2), then per image L_b, s_b, t_b (kind 1: 1 - rho_b, rho_b,
+ * 0); an image with W = 0 adds 0 to an L1 loss and has NaN for its three values.  stats (batch, 18) doubles carries the
+ * per-image scalars from the forward to the backward on the device.  Backward: d_depth (batch, height, width),
+ * contiguous, = *g_loss (one value on the device) times the exact gradient of the loss, the fit differentiated through:
+ *   affine  dL_b / dx_k = w_k / W (sgn r_k - B / W - (A - B pm)(p_k - pm) / var_p),  A = sum w sgn(r) p, B = sum w sgn(r)
+ *   scale   dL_b / dx_k = w_k / W (sgn r_k - A p_k / sum w p^2),   none  w_k / W sgn r_k,   sgn 0 = 0
+ *   Pearson drho / dx_k = w_k ((p_k - pm) / sqrt(var_p var_x) - rho (x_k - xm) / var_x);   inverse: times -1 / depth_k^2
+ * (a degenerate fit drops the term that divides by the vanishing sum).  The float entry points read floats and compute
+ * in double up to the one rounding of each output; the _f64 ones are the same templates on double.  Every sum has one
+ * order given the shapes, no atomics: outputs repeat bit for bit.  scratch: gs_depth_loss_scratch_bytes, 8-byte aligned.
+ * Sizes below 1, a NULL depth / prior / output / stats, overlapping strides: -1; batch * height * width >= 2^31, a batch
+ * above 65535 or an unknown kind / align / inverse: -2; a NULL or misaligned scratch: -1, a short one: -4; all before
+ * any launch.  gs_depth_loss_scratch_bytes returns the same negative codes. */
+int64_t gs_depth_loss_scratch_bytes(int64_t batch, int64_t height, int64_t width);
+int gs_depth_loss_fwd(int64_t batch, int64_t height, int64_t width, const float* depth, int64_t depth_batch_stride,
+                      int64_t depth_row_stride, int64_t depth_pixel_stride, const float* prior,
+                      int64_t prior_batch_stride, int64_t prior_row_stride, int64_t prior_pixel_stride,
+                      const float* weight, int64_t weight_batch_stride, int64_t weight_row_stride,
+                      int64_t weight_pixel_stride, int32_t kind, int32_t align, int32_t inverse, float* results,
+                      double* stats, void* scratch, int64_t scratch_bytes, void* stream);
+int gs_depth_loss_bwd(int64_t batch, int64_t height, int64_t width, const float* depth, int64_t depth_batch_stride,
+                      int64_t depth_row_stride, int64_t depth_pixel_stride, const float* prior,
+                      int64_t prior_batch_stride, int64_t prior_row_stride, int64_t prior_pixel_stride,
+                      const float* weight, int64_t weight_batch_stride, int64_t weight_row_stride,
+                      int64_t weight_pixel_stride, int32_t kind, int32_t align, int32_t inverse, const double* stats,
+                      const float* g_loss, float* d_depth, void* stream);
+int gs_depth_loss_fwd_f64(int64_t batch, int64_t height, int64_t width, const double* depth, int64_t depth_batch_stride,
+                          int64_t depth_row_stride, int64_t depth_pixel_stride, const double* prior,
+                          int64_t prior_batch_stride, int64_t prior_row_stride, int64_t prior_pixel_stride,
+                          const double* weight, int64_t weight_batch_stride, int64_t weight_row_stride,
+                          int64_t weight_pixel_stride, int32_t kind, int32_t align, int32_t inverse, double* results,
+                          double* stats, void* scratch, int64_t scratch_bytes, void* stream);
+int gs_depth_loss_bwd_f64(int64_t batch, int64_t height, int64_t width, const double* depth, int64_t depth_batch_stride,
+                          int64_t depth_row_stride, int64_t depth_pixel_stride, const double* prior,
+                          int64_t prior_batch_stride, int64_t prior_row_stride, int64_t prior_pixel_stride,
+                          const double* weight, int64_t weight_batch_stride, int64_t weight_row_stride,
+                          int64_t weight_pixel_stride, int32_t kind, int32_t align, int32_t inverse,
+                          const double* stats, const double* g_loss, double* d_depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,9 +4,10 @@ operator API of taichi_splatting (reference taichi_splatting/__init__.py:1-33).
 Compute backend: hand-written HIP kernels for gfx950 in libgsplat_hip.so (C-ABI:
 include/gsplat_hip.h), called through ctypes.  There is no other backend.
 """
-from . import appearance, environment, hip_lib, losses, mip, perspective
+from . import appearance, depth, environment, hip_lib, losses, mip, perspective
 from . import hip_lib as cuda_lib  # drop-in alias for `taichi_splatting.cuda_lib`
 from .data_types import Gaussians2D, Gaussians3D, RasterConfig
+from .depth import depth_prior_loss, fit_scale_shift, pearson_depth_loss
 from .densify import DensifyPlan, DensifyStats, densify, move_rows, plan_densify, split_gaussians3d
 from .environment import composite_environment, constant_environment, environment_directions, sample_environment
 from .mapper.tile_mapper import map_to_tiles, pad_to_tile
@@ -52,6 +53,7 @@ __all__ = [
     'rasterize', 'rasterize_with_tiles',
     'perspective', 'hip_lib', 'cuda_lib', 'losses', 'appearance',
     'environment', 'composite_environment', 'sample_environment', 'environment_directions', 'constant_environment',
+    'depth', 'depth_prior_loss', 'pearson_depth_loss', 'fit_scale_shift',
     'TaichiQueue', 'taichi_queue',
     'install_as_taichi_splatting',
 ]

@@ -268,6 +268,13 @@ SIGNATURES = {
     "gs_envmap_bwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] + [_P] * 6 + [_I64, _P]),
     "gs_envmap_fwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] * 2 + [_P] * 4),
     "gs_envmap_bwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64] + [_P, _I64, _I64] + [_P] * 6 + [_I64, _P]),
+    # depth: losses against a depth prior (depth, prior and weight with three strides each, kind, align, inverse)
+    "gs_depth_loss_scratch_bytes": (_I64, [_I64] * 3),
+    "gs_depth_loss_fwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 3 + [_I32] * 3 + [_P] * 3 + [_I64, _P]),
+    "gs_depth_loss_bwd": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 3 + [_I32] * 3 + [_P] * 4),
+    "gs_depth_loss_fwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 3 + [_I32] * 3 + [_P] * 3 +
+                              [_I64, _P]),
+    "gs_depth_loss_bwd_f64": (ctypes.c_int, [_I64] * 3 + [_P, _I64, _I64, _I64] * 3 + [_I32] * 3 + [_P] * 4),
 }
 
 _lib = None
